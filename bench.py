@@ -6,9 +6,13 @@ as plain ``python bench.py --gpus N`` -- it starts the N ranks itself the same w
 WORLD_SIZE that is not N, or fewer visible GPUs than N, is an error, never a silently smaller run.  One rank per GPU, RCCL.  One "step" = zero_grad ->
 forward (both towers) -> ClipLoss (packed feature all-gather + global logits when N>1) -> backward (DDP bucketed
 grad all-reduce overlapped) -> AdamW step -> logit_scale clamp, on synthetic inputs already resident in HBM.
-Rank 0 prints ONE JSON line.  ``roofline`` prices the dominant kernel (the NT MFMA GEMM) from HIP events recorded
-around every one of its launches inside the timed region; ``cpu_baseline`` times the reference's own train_one_epoch
-(from oracle/_ref/reference_src.zip on the GPU box; the CPU oracle -- the port -- when that is missing) on the host cores for a bounded sample (N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline (``value``, ``ms_per_step``, the
+configuration); ``--dump-outputs DIR`` runs the reproducible form of the step (``--deterministic``) and writes what the last timed step
+computed as float32 .npy files (``dump_outputs``).  ``--full`` adds
+everything else: ``roofline`` prices the dominant kernel (the NT MFMA GEMM) from HIP events recorded around every one of its launches in
+the event-timed steps (every 20th timed step; every 2nd with --serial-towers); ``cpu_baseline`` times the reference's own train_one_epoch
+(from oracle/_ref/reference_src.zip on the GPU box; the CPU oracle -- the port -- when that is missing) on the host cores for a bounded
+sample (N=1 only); the clock sample, the eager baseline, the further samples of the same step and the config 4 / 5 lines.
 """
 import argparse
 import json
@@ -111,7 +115,23 @@ def parse():
     ap.add_argument("--gemm-variant", type=int, default=0, help="developer: value for ocn_set_gemm_variant (kernel choice / ablation knobs)")
     ap.add_argument("--tuning", action="append", default=[], metavar="KEY=VALUE", help="developer: ocn_set_tuning(KEY, VALUE) before the run")
     ap.add_argument("--dist-backend", default="nccl", help="developer: 'gloo' + OCN_BENCH_ONE_DEVICE=1 runs N ranks on one GPU")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: the roofline (HIP events around the GEMM launches of every "
+                    "20th timed step, every 2nd with --serial-towers), the clock sample, the dense-text / reference-work / fp32-stream / accum8 "
+                    "samples, the eager and CPU baselines and the config 4 / 5 lines (each still switched off by its --no-* option).  Without it "
+                    "a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed to DIR/<name>.npy (float32): "
+                    "the loss, the forward's outputs and a fixed seeded sample of every parameter's gradient and updated value (dump_outputs).  "
+                    "Implies --deterministic, so that two runs with the same arguments write the same bits")
+    args = ap.parse_args()
+    if args.dump_outputs:
+        # the default step adds gradients and loss terms with fp32 atomics in a varying order; over the steps the bf16 streams amplify those
+        # last-bit differences (25 steps of ViT-B-32: features 0.8 % apart, gradients 3 %; profiles/bench_dump_reproducibility.txt), so
+        # outputs meant for comparison come from the reproducible form of the same step
+        args.deterministic = True
+    if not args.full:  # a plain run measures the headline only
+        args.no_roofline = args.no_clock_sample = args.no_dense_text_line = args.no_extra_lines = args.no_config_lines = True
+        args.no_cpu_baseline = args.no_eager_baseline = True
+    return args
 
 
 NT_KERNEL = {0: "gemm_nt5_kernel<0,false,0> (plain bf16 out)", 1: "gemm_nt5_kernel<1,false,2> (bias + GELU, saves gelu' in 8 bits)",
@@ -190,6 +210,44 @@ def roof(a):
     fh = a["gbps"] / HBM_ACHIEVABLE_GBPS
     return {"bound": "mfma" if fm >= fh else "hbm", "frac": round(max(fm, fh), 4), "frac_mfma": round(fm, 4), "frac_hbm": round(fh, 4),
             "frac_hbm_of_spec": round(a["gbps"] / HBM_SPEC_GBPS, 4), "algorithmic_gb_per_s": round(a["gbps"], 1)}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _rows_sample(t, max_bytes):
+    """``t`` as float32 on the host; a fixed, seeded, sorted subset of its rows when the whole would exceed ``max_bytes`` (the same rows for
+    every tensor of one length: image and text features stay paired)"""
+    t = t.detach().float()
+    if t.dim() >= 1 and t.numel() * 4 > max_bytes:
+        keep = max(1, max_bytes // (4 * max(1, t[0].numel())))
+        idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        t = t[idx.to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(path, loss, out, model, per_param=2048):
+    """``--dump-outputs``: what the last timed step handed its caller, as float32 ``path/<name>.npy``: ``loss``; the forward's outputs as the loss
+    received them (``image_features``, ``text_features``, ``logit_scale``, ``logit_bias`` with SigLIP; a seeded sample of rows beyond 16 MB each);
+    ``grad_sample`` / ``param_sample``: the same seeded ``per_param`` positions (all of them for smaller tensors) of every parameter, in
+    ``named_parameters`` order, of that step's gradient (NaN where a parameter has none) and of the value its optimizer step left"""
+    import numpy as np
+    arrays = {"loss": np.asarray(float(loss.detach()), dtype=np.float32)}
+    arrays.update({k: _rows_sample(v, 16 << 20) for k, v in out.items()})
+    g = torch.Generator().manual_seed(0)
+    grads, params = [], []
+    for _, p in model.named_parameters():
+        n = p.numel()
+        idx = (torch.arange(n) if n <= per_param else torch.randint(0, n, (per_param,), generator=g).sort().values).to(p.device)
+        params.append(p.detach().reshape(-1)[idx].float())
+        grads.append(p.grad.reshape(-1)[idx].float() if p.grad is not None else torch.full((len(idx),), float("nan"), device=p.device))
+    arrays["grad_sample"] = torch.cat(grads).cpu().numpy()
+    arrays["param_sample"] = torch.cat(params).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def _reference_cpu_record():
@@ -458,8 +516,8 @@ def config_line(extra_args, what, steps=4, warmup=1, timeout=300):
     `steps` timed steps of which the first carries HIP events on every GEMM launch (its towers one at a time), so the record has the per-kernel
     roofline of THAT model; returns the sub-record that rides on the default line, or {"error": ...} -- a sample never takes the line down"""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-eager-baseline",
-           "--no-dense-text-line", "--no-extra-lines", "--no-clock-sample", "--no-config-lines"] + extra_args
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline",
+           "--no-eager-baseline", "--no-dense-text-line", "--no-extra-lines", "--no-clock-sample", "--no-config-lines"] + extra_args
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     try:
         t0 = time.perf_counter()
@@ -611,6 +669,11 @@ def run(args, rank, local_rank, world, dev, rank_devices, one_device):
         timer.install()
 
     step_no = [0]
+    last_out = {} if args.dump_outputs else None  # --dump-outputs: what the loss of the latest step was handed
+
+    def keep(d):
+        if last_out is not None:
+            last_out.update({k: v.detach() for k, v in d.items()})
 
     def micro_batches(mb):
         """device batches of this optimizer step; with --h2d each one arrives from pinned host memory while the previous one computes"""
@@ -634,6 +697,7 @@ def run(args, rank, local_rank, world, dev, rank_devices, one_device):
             b = next(iter(micro_batches(mb)))
             out = net(image=b["image"], text=b["text"])
             loss = loss_fn(**out)
+            keep(out)
             loss.backward()
             if grad_sync is not None:
                 grad_sync.finish()
@@ -661,6 +725,7 @@ def run(args, rank, local_rank, world, dev, rank_devices, one_device):
                     loss.backward()
                 if pipe is not None:
                     pipe.release(b)
+            keep(dict(inputs, logit_scale=o["logit_scale"], **extra_in))
             if grad_sync is not None:
                 grad_sync.finish()
         opt.step()
@@ -703,6 +768,8 @@ def run(args, rank, local_rank, world, dev, rank_devices, one_device):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
     final_loss = float(loss.detach())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, loss, last_out, model)
     if rank == 0:
         # the headline, as soon as the K timed steps are over: the one JSON line on stdout also carries the auxiliary samples and baselines
         # (minutes of further work) -- a driver that kills the process in that window still finds the measured value here
@@ -826,7 +893,7 @@ def run(args, rank, local_rank, world, dev, rank_devices, one_device):
                        "grad_checkpointing": (f"block recompute (transformer.py:577-585) for all but the last {kept_blocks[0]} image / {kept_blocks[1]} text blocks, whose "
                                               f"activations stay in HBM (--keep-blocks {args.keep_blocks}); {recompute_share:.2f} of a forward is recomputed per step"
                                               if args.grad_checkpointing else "off"),
-                       "random_init_weights": True, "final_loss": round(final_loss, 4)},
+                       "random_init_weights": True, "deterministic": bool(args.deterministic), "final_loss": round(final_loss, 4)},
             # FLOPs of the model as the reference runs it (every caption padded to context_length); the packed text tower executes fewer
             ("step_model_tflops_per_gpu" if not model_ref.pack_text else "step_dense_equivalent_model_tflops_per_gpu"): round(value / world * flops_pair / 1e3, 1),
             "peak_hbm_gb_rank0": round(peak_bytes / 1e9, 1), "reserved_hbm_gb_rank0": round(torch.cuda.max_memory_reserved() / 1e9, 1),

@@ -15,6 +15,9 @@ Fixtures (all fp32 CPU, ``torch.use_deterministic_algorithms(True)``):
   dist_loss_w2.npz   ``ClipLoss`` (3 gather modes) and ``SigLipLoss`` ('bidir') under gloo, world_size 2/3:
                      per-rank loss and feature grads on random unit features
 Large grads are stored as (L2 norm, sum, 4096-element strided sample); small ones in full.
+The reference's own data tables, copied as they are (``tables``):
+  reference_vit_model_configs.json  every ``src/open_clip/model_configs/ViT-*.json``, keyed by model name
+  reference_model_profile.csv       ``docs/model_profile.csv`` (parameters and forward GFLOPs per model)
 """
 import os
 import sys
@@ -248,11 +251,25 @@ def make_dist(world, port):
     print(f"dist_loss_w{world}.npz", {k: float(v) for k, v in out.items() if k.endswith("/loss")})
 
 
+def make_reference_tables():
+    import glob
+    import json
+    import shutil
+    from oracle.ref_shim import REFERENCE_SRC
+    cfg_dir = os.path.join(REFERENCE_SRC, "open_clip", "model_configs")
+    cfgs = {os.path.basename(f)[:-5]: json.load(open(f)) for f in sorted(glob.glob(os.path.join(cfg_dir, "ViT-*.json")))}
+    with open(os.path.join(GOLD, "reference_vit_model_configs.json"), "w") as fh:
+        json.dump(cfgs, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    shutil.copyfile(os.path.join(os.path.dirname(REFERENCE_SRC), "docs", "model_profile.csv"), os.path.join(GOLD, "reference_model_profile.csv"))
+    print("reference_vit_model_configs.json", len(cfgs), "configs; reference_model_profile.csv")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.use_deterministic_algorithms(True)
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["tiny", "siglip", "quickgelu", "hd88", "dist", "vitb32"]
+    which = sys.argv[1:] or ["tiny", "siglip", "quickgelu", "hd88", "dist", "vitb32", "tables"]
     if "tiny" in which:
         make_tiny(False)
     if "siglip" in which:
@@ -267,3 +284,5 @@ if __name__ == "__main__":
         make_dist(8, 29613)  # the 8-rank world of BASELINE config 3
     if "vitb32" in which:
         make_vitb32()
+    if "tables" in which:
+        make_reference_tables()

@@ -18,7 +18,7 @@ COMMON = ["--model", "small-test", "--local-batch", "8", "--steps", "3", "--warm
 
 def _bench(extra, nproc=1, env=None, roofline=False, launcher=True):
     e = dict(os.environ, **(env or {}))
-    common = [a for a in COMMON if roofline is False or a != "--no-roofline"]
+    common = [a for a in COMMON if roofline is False or a != "--no-roofline"] + (["--full"] if roofline else [])
     if nproc == 1 or not launcher:  # launcher=False: plain `python bench.py --gpus N`, as the driver calls it
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc)] + common + extra
     else:
@@ -52,6 +52,47 @@ def test_bench_default_line_mixes_event_timed_and_overlapped_steps():
     # (three optimizer steps at lr 1e-3 on the miniature model amplify the summation-order noise of the fp32 atomics: measured up to 4e-3)
     assert abs(with_ev["config"]["final_loss"] - without["config"]["final_loss"]) < 3e-2, (with_ev["config"]["final_loss"], without["config"]["final_loss"])
     assert with_ev["reserved_hbm_gb_rank0"] <= 1.5 * without["reserved_hbm_gb_rank0"] + 0.5  # one allocator pool per stream in BOTH kinds of step
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and carries the headline only (no roofline, clock sample, further samples or
+    baselines); --dump-outputs writes the last timed step's loss, features, logit scale and the seeded gradient / parameter samples as float32
+    .npy files within 64 MB; it runs the reproducible form of the step, so two runs with the same arguments write the same values.  The step
+    counts are the ones run: 3 timed steps after 1 warm-up step leave exactly the state of 4 timed steps, and a different one from 3 steps; the
+    dumped loss is the CLIP loss of the dumped features and logit scale (recomputed on the host with the loss's bf16 operands)"""
+    import numpy as np
+    import torch
+    from oracle import clip_oracle as O
+    plain = [a for a in COMMON if a not in ("--no-cpu-baseline", "--no-eager-baseline", "--no-roofline")]
+
+    def run(tag, extra=()):
+        d = tmp_path / tag
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + plain + list(extra) + ["--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+
+    (line, a), (_, b) = run("a"), run("b")
+    (line4, c), (line31, e) = run("steps4", ["--steps", "4"]), run("steps3_warmup1", ["--warmup", "1"])
+    assert line["steps"] == 3 and line["warmup"] == 0 and line["ms_per_step"] > 0 and line["value"] > 0 and line["config"]["deterministic"] is True
+    assert (line4["steps"], line4["warmup"], line31["steps"], line31["warmup"]) == (4, 0, 3, 1)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert not {"roofline", "clock_under_load", "dense_text_tower", "torch_eager_baseline", "cpu_baseline"} & set(line)
+    assert {"loss", "image_features", "text_features", "logit_scale", "grad_sample", "param_sample"} <= set(a)
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["image_features"].shape == a["text_features"].shape == (8, 128)
+    assert np.isfinite(a["grad_sample"]).all() and np.isfinite(a["param_sample"]).all() and a["grad_sample"].size == a["param_sample"].size
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+        assert np.array_equal(c[k], e[k]), k
+    assert not np.array_equal(a["param_sample"], c["param_sample"])
+    i, t, s = (torch.from_numpy(a[k]) for k in ("image_features", "text_features", "logit_scale"))
+    bf = lambda x: x.bfloat16().float()  # noqa: E731
+    ref = (O.cross_entropy_arange(bf(s * i) @ bf(t).t()) + O.cross_entropy_arange(bf(s * t) @ bf(i).t())) / 2
+    assert abs(float(ref) - float(a["loss"])) < 1e-3, (float(ref), float(a["loss"]))
 
 
 def test_bench_accumulation_and_host_fed_modes():

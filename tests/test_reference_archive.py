@@ -14,9 +14,10 @@ import pytest
 from oracle.ref_shim import reference_available
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
 
 
+@needs_reference
 def test_archive_holds_the_two_packages_and_nothing_else():
     from oracle import fetch_ref
     path = fetch_ref.fetch()
@@ -34,6 +35,7 @@ def test_archive_holds_the_two_packages_and_nothing_else():
     assert tracked == ""
 
 
+@needs_reference
 def test_reference_train_one_epoch_runs_from_the_archive(tmp_path):
     """as on the GPU box: /root/reference hidden (ref_shim.REFERENCE_SRC pointed at nothing), two steps of the reference's loop from the archive"""
     out = tmp_path / "ref.json"

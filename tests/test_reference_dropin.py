@@ -1,17 +1,21 @@
-"""CPU, only where /root/reference exists (never on the GPU box): the native modules plug into the REFERENCE's own objects.
+"""CPU, where the reference's source tree is present (never on the GPU box): the native modules plug into the REFERENCE's own objects.
   * ``native.load_state_dict(reference_model.state_dict())`` is strict-clean (same names and shapes);
   * ``open_clip.task.CLIPTask(native_model, loss=NativeClipLoss())`` constructs, exposes the native module as its trainable
     module and drives it with the reference's call convention (``image=``, ``text=``) -- on CPU the call must stop at the first
     kernel with the 'no CPU path' error, i.e. nothing in between silently computes;
   * the reference's weight-decay grouping (open_clip_train/optim.py:136-208) applied to the native model partitions the
     parameters exactly like ``param_groups_like_reference``.
-The reference is test infrastructure here (imported through oracle/ref_shim.py); the product never imports it."""
+The reference is test infrastructure here (imported through oracle/ref_shim.py); the product never imports it.  The registry and FLOP
+checks read the reference's data tables from tests/golden/ (oracle/make_golden.py copies them) and run everywhere."""
+import os
+
 import pytest
 import torch
 
 from oracle.ref_shim import import_reference, reference_available
 
-pytestmark = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not reference_available(), reason="reference tree not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _pair():
@@ -24,6 +28,7 @@ def _pair():
     return open_clip, ref, native.to_empty(device="cpu")
 
 
+@needs_reference
 def test_native_model_is_a_drop_in_for_the_reference_task_and_optimizer_grouping():
     open_clip, ref, native = _pair()
     missing, unexpected = native.load_state_dict(ref.state_dict(), strict=True)
@@ -52,6 +57,7 @@ def test_native_model_is_a_drop_in_for_the_reference_task_and_optimizer_grouping
     assert {wd: {names[i] for i in ids} for wd, ids in by_wd(mine).items()} == ref_own
 
 
+@needs_reference
 def test_reference_train_one_epoch_drives_the_native_task():
     """The reference's unmodified ``train_one_epoch`` (open_clip_train/train.py:337) accepts a TrainState built from the native
     model, loss and optimizer and reaches the native forward with the batch it prepared (on CPU: the 'no CPU path' error of
@@ -85,6 +91,7 @@ def test_reference_train_one_epoch_drives_the_native_task():
         train_one_epoch(TrainState(task=task, optimizer=opt), {"train": Data()}, args)
 
 
+@needs_reference
 def test_layer_groups_and_partial_locks_match_the_reference():
     """``visual.layer_groups()`` / the text groups name the same partitions as the reference's (transformer.py:718-743, :1999-2031) and
     ``lock_image_tower(unlocked_groups=k)`` / ``lock_text_tower(unlocked_layers=k)`` freeze exactly the same parameters"""
@@ -112,23 +119,21 @@ def test_layer_groups_and_partial_locks_match_the_reference():
 
 def test_registered_configs_equal_the_reference_jsons(tmp_path):
     """every reference-named config of the native registry carries exactly the reference JSON's values; every plain-ViT JSON the native
-    path can run is registered; add_model_config(path) (the reference's form, factory.py:80-85) loads JSON files"""
-    import glob
+    path can run is registered; add_model_config(path) (the reference's form, factory.py:80-85) loads JSON files.  The reference's
+    model_configs/ViT-*.json are read from tests/golden/reference_vit_model_configs.json (name -> the file's contents)"""
     import json
-    import os
     from open_clip_amd import configs
     from open_clip_amd.model import NativeCLIP
-    ref_dir = "/root/reference/src/open_clip/model_configs"
-    names = [n for n in configs.list_models() if os.path.exists(os.path.join(ref_dir, n + ".json"))]  # (other tests register their own)
+    with open(os.path.join(GOLDEN, "reference_vit_model_configs.json")) as fh:
+        ref_cfgs = json.load(fh)
+    names = [n for n in configs.list_models() if n in ref_cfgs]  # (other tests register their own)
     assert len(names) >= 31
     for n in names:
-        with open(os.path.join(ref_dir, n + ".json")) as fh:
-            assert json.load(fh) == configs._MODEL_CONFIGS[n], n
+        assert ref_cfgs[n] == configs._MODEL_CONFIGS[n], n
     # the other way round: a reference ViT config that passes the native path's own option check must be registered
     missing = []
-    for f in sorted(glob.glob(os.path.join(ref_dir, "ViT-*.json"))):
-        d = json.load(open(f))
-        name = os.path.basename(f)[:-5]
+    for name in sorted(ref_cfgs):
+        d = ref_cfgs[name]
         kw = {k: v for k, v in d.items() if k not in ("embed_dim", "vision_cfg", "text_cfg", "quick_gelu")}
         try:
             NativeCLIP._check_cfg(d["vision_cfg"], d["text_cfg"], kw)
@@ -151,10 +156,10 @@ def test_registered_configs_equal_the_reference_jsons(tmp_path):
 
 def test_analytic_forward_flops_match_the_reference_profile_table():
     """bench.py prices every model against the MFMA roof with configs.forward_gflops_per_pair: it must agree with the reference's own
-    docs/model_profile.csv (the figure SURVEY.md 8d quotes) for every registered config the table lists"""
+    docs/model_profile.csv (the figure SURVEY.md 8d quotes; tests/golden/reference_model_profile.csv) for every registered config the table lists"""
     import csv
     from open_clip_amd import configs
-    with open("/root/reference/docs/model_profile.csv") as fh:
+    with open(os.path.join(GOLDEN, "reference_model_profile.csv")) as fh:
         table = {r["model"]: float(r["gflops"]) for r in csv.DictReader(fh)}
     seen = 0
     for name in configs.list_models():
@@ -165,6 +170,7 @@ def test_analytic_forward_flops_match_the_reference_profile_table():
     assert seen >= 28
 
 
+@needs_reference
 def test_reference_stream_dtypes_under_autocast():
     """What ``NativeCLIP(image_stream="bf16")`` mirrors, read off the REFERENCE itself (round 6): under ``--precision amp_bf16`` (torch.autocast,
     precision.py:6-17) the image tower's residual stream is bf16 from ln_pre on -- conv1 runs under autocast (transformer.py:794), LayerNorm hands its
@@ -187,6 +193,7 @@ def test_reference_stream_dtypes_under_autocast():
     assert seen["text block"] == (torch.float32, torch.float32)
 
 
+@needs_reference
 def test_create_task_mirrors_the_reference_dispatch():
     """open_clip_amd.create_task(args, model) makes the choices of open_clip.factory.create_task (factory.py:975-1043) from the reference's own parsed
     arguments -- task class, loss kind, local_loss / gather_with_grad / rank / world_size / loss_dist_impl -- with the native losses inside the

@@ -1,4 +1,4 @@
-"""markdown table of DESIGN.md section 5 from a bench line (+ the PMC passes of the same sources): python tools/design_table.py bench.log pmc_traffic.json mfma_util.txt"""
+"""markdown table of DESIGN.md section 5 from a `bench.py --full` line (+ the PMC passes of the same sources): python tools/design_table.py bench.log pmc_traffic.json mfma_util.txt"""
 import json
 import re
 import sys

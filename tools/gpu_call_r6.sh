@@ -16,8 +16,8 @@ if has tests; then
   cp $O/parity_report.txt $O/${TAG}_parity_report.txt 2>/dev/null
   timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3 > $O/${TAG}_smoke.log; stamp tests
 fi
-if has bench; then timeout 1500 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.log 2> $O/${TAG}_bench.err; stamp bench; fi
-if has benchquick; then timeout 600 python bench.py --steps 20 --warmup 5 $QUIET ${BENCH_ARGS} > $O/${TAG}_benchquick.log 2>&1; stamp benchquick; fi
+if has bench; then timeout 1500 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.log 2> $O/${TAG}_bench.err; stamp bench; fi
+if has benchquick; then timeout 600 python bench.py --full --steps 20 --warmup 5 $QUIET ${BENCH_ARGS} > $O/${TAG}_benchquick.log 2>&1; stamp benchquick; fi
 if has streams; then  # the three residual-stream modes of the image tower, alternating processes
   for i in 1 2; do for m in fp32 bf16 bf16-fp32grad; do
     timeout 300 python bench.py --steps 12 --warmup 3 --no-roofline $QUIET --image-stream $m 2>&1 | grep '^{' >> $O/${TAG}_streams_$m.json

@@ -17,7 +17,8 @@ block by block while the backward is still running, and block-granular recompute
 is a flag of the same Function.
 """
 import math
-from typing import Optional
+from collections import namedtuple
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -38,14 +39,8 @@ def _round_up(a, b):
 class _WeightCache:
     def __init__(self):
         self._d = {}
-        self.pair_wgrad = True  # block backward: run the wgrad GEMMs on a side stream under the HBM-bound kernels (_Paired)
-        self.deterministic = False  # weight / bias gradient GEMMs in their reproducible form (ocn_gemm_tn_accum_det)
-        self.single_query = True  # pooled last block (head_dim 64): K, V projection only + single-query attention (_pooled_block_forward)
         self._side = _StreamMap()  # wgrad side streams of this tower, one per (device, main stream)
         self.twin_stats = {"hit": 0, "miss": 0}  # how often a block's backward found the bf16 twin of its incoming gradient (tests assert it does)
-        # residual stream of THIS tower: "fp32" | "bf16" (stream and its gradient bf16: the reference's autocast in the image tower) |
-        # "bf16-fp32grad" (bf16 stream; the gradient travels as bf16 with an fp32 companion for the residual path, see _publish_f32)
-        self.stream = "fp32"
 
     def side_stream(self, dev):
         """the wgrad stream that belongs to the CURRENT stream (one per main stream: the towers may run on streams of their own)"""
@@ -85,9 +80,20 @@ class _WeightCache:
     def __deepcopy__(self, memo):
         """a copied model (EMA twin, base_task.py:171) has new parameter addresses: none of the cached operand copies could ever hit
         there, so the copy starts empty instead of duplicating every bf16 weight"""
-        new = _WeightCache()
-        new.pair_wgrad, new.deterministic, new.single_query, new.stream = self.pair_wgrad, self.deterministic, self.single_query, self.stream
-        return new
+        return _WeightCache()
+
+
+class _Exec(NamedTuple):
+    """How ONE tower runs ONE call: its operand cache and the execution switches, built from the model's public attributes when the call starts
+    (``NativeCLIP._exec_options``) and handed down to every autograd Function of the tower, whose backward reads the same value -- nothing is
+    stored between calls, so a switch flipped on the model holds for the next call on every path."""
+    cache: _WeightCache
+    pair_wgrad: bool = True  # block backward: run the wgrad GEMMs on a side stream under the HBM-bound kernels (_Paired)
+    deterministic: bool = False  # weight / bias gradient GEMMs in their reproducible form (ocn_gemm_tn_accum_det)
+    single_query: bool = True  # pooled last block (head_dim 64): K, V projection only + single-query attention (_pooled_block_forward)
+    # residual stream of THIS tower: "fp32" | "bf16" (stream and its gradient bf16: the reference's autocast in the image tower) |
+    # "bf16-fp32grad" (bf16 stream; the gradient travels as bf16 with an fp32 companion for the residual path, see _publish_f32)
+    stream: str = "fp32"
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -97,7 +103,6 @@ class _WeightCache:
 # (an attribute on the tensor object autograd hands from one Function's backward to the next, stamped with the tensor's
 # version counter): nothing is keyed by address, nothing outlives the tensor, and a consumer that receives any other
 # tensor (autograd summed two branches, a hook replaced the gradient, ...) finds no attribute and casts.
-# ------------------------------------------------------------------------------------------------------
 # ------------------------------------------------------------------------------------------------------
 
 def _publish_twin(g32, g16, colsum=None):
@@ -131,6 +136,35 @@ def _take_twin(g32, cache=None):
     if cache is not None:
         cache.twin_stats["hit" if hit else "miss"] += 1
     return tw[0] if hit else ops.cast_bf16(g32)
+
+
+def _take_grad(dy, x, ex):
+    """(with _hand_down: the two ends of a block's backward, shared by _BlockFn and _PooledBlockFn)  A block with input ``x`` receives ``dy``
+    -> (bf16 GEMM operand, the value the residual path adds, fp32 column sums | None, want_f32).
+    fp32 ``dy``: the bf16 twin that came with it (or a cast) and ``dy`` itself.  bf16 ``dy``: it IS the bf16 GEMM operand; the residual path adds it in
+    bf16, or from its fp32 companion (``bf16-fp32grad``).  Only the head publishes column sums (B rows: free): the LAST block's c_proj bias gradient.
+    ``want_f32``: does the LayerNorm backward that produces dx write it in fp32 beside the bf16 it always writes?  Not for a bf16 ``x``, where the
+    bf16 tensor is the gradient -- unless ``bf16-fp32grad`` sends the fp32 value along (_hand_down publishes either pair)."""
+    colsum, want_f32 = _take_colsum(dy), (x.dtype != BF16 or ex.stream == "bf16-fp32grad")
+    if dy.dtype == BF16:
+        dy16 = dy.contiguous()
+        dres = _take_f32(dy) if ex.stream == "bf16-fp32grad" else None
+        return dy16, (dy16 if dres is None else dres), colsum, want_f32
+    return _take_twin(dy, ex.cache), dy.contiguous(), colsum, want_f32
+
+
+def _hand_down(ctx, x, dx, dx16, grads, need_w):
+    """what a block's backward returns: the gradient of its input ``x`` in the stream's dtype, with its other form published beside it (the bf16 twin of
+    an fp32 gradient; the fp32 companion, if any, of a bf16 one), the 12 parameter gradients (None when no parameter of the block trains) and
+    None for every argument behind them"""
+    if x.dtype == BF16:
+        _publish_f32(dx16, dx)
+        dx = dx16
+    else:
+        _publish_twin(dx, dx16)
+    if not need_w:
+        grads = [None] * len(grads)
+    return (dx, *grads, *[None] * (len(ctx.needs_input_grad) - 1 - len(grads)))
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -210,6 +244,14 @@ class _Paired:
 # ------------------------------------------------------------------------------------------------------
 # residual block (transformer.py:319-330)
 # ------------------------------------------------------------------------------------------------------
+# the 12 parameters of a residual block, in the order the block Functions take them behind ``x``
+_BlockParams = namedtuple("_BlockParams", "ln1w ln1b wqkv bqkv wo bo ln2w ln2b wfc bfc wproj bproj")
+# what a block's backward needs besides tensors (``ctx.meta``); ``ex``: the _Exec of the call
+_BlockMeta = namedtuple("_BlockMeta", "ex B L heads causal recompute seq_off act")
+# activations the full block keeps for its backward (or recomputes there)
+_BlockSaved = namedtuple("_BlockSaved", "mean1 rstd1 h1 qkv a lse xmid mean2 rstd2 h2 f g")
+
+
 def _grad_arena(p):
     """one zeroed fp32 allocation carved into views shaped like the tensors of ``p`` (the wgrad / LayerNorm kernels accumulate into it)"""
     sizes = [q.numel() for q in p]
@@ -218,72 +260,56 @@ def _grad_arena(p):
     for q, n in zip(p, sizes):
         grads.append(arena[o:o + n].view(q.shape))
         o += n
-    return grads
+    return _BlockParams(*grads)
 
 
-def _block_forward(x, p, cache, B, L, heads, causal, seq_off=None, act=ops.EPI_BIAS_GELU):
-    (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj) = p
+def _block_forward(x, p, ex, B, L, heads, causal, seq_off=None, act=ops.EPI_BIAS_GELU):
+    cache = ex.cache
     M, C = x.shape
-    h1, _, mean1, rstd1 = ops.layernorm_fwd(x, ln1w, ln1b)
-    qkv = ops.gemm_nt(ops.EPI_BF16, h1, cache.get(wqkv, "n"), ops.empty((M, 3 * C), BF16, x), bias=bqkv)
+    h1, _, mean1, rstd1 = ops.layernorm_fwd(x, p.ln1w, p.ln1b)
+    qkv = ops.gemm_nt(ops.EPI_BF16, h1, cache.get(p.wqkv, "n"), ops.empty((M, 3 * C), BF16, x), bias=p.bqkv)
     hd = C // heads
     a, lse = ops.attn_fwd(qkv, B, L, heads, causal, hd ** -0.5, hd, seq_off)
     # the residual stream keeps the dtype it arrives in: fp32, or bf16 (image tower, ``image_stream="bf16"``: LayerNorm reads bf16, the residual
     # epilogue adds in bf16 as the reference's autocast does -- ops.EPI_BIAS_RESID_BF16)
     epi_res = ops.EPI_BIAS_RESID_BF16 if x.dtype == BF16 else ops.EPI_BIAS_RESID_F32
-    xmid = ops.gemm_nt(epi_res, a, cache.get(wo, "n"), ops.empty((M, C), x.dtype, x), bias=bo, resid=x)
-    h2, _, mean2, rstd2 = ops.layernorm_fwd(xmid, ln2w, ln2b)
-    Fd = wfc.shape[0]
+    xmid = ops.gemm_nt(epi_res, a, cache.get(p.wo, "n"), ops.empty((M, C), x.dtype, x), bias=p.bo, resid=x)
+    h2, _, mean2, rstd2 = ops.layernorm_fwd(xmid, p.ln2w, p.ln2b)
+    Fd = p.wfc.shape[0]
     f = ops.empty((M, Fd), torch.uint8, x)  # gelu'(pre-activation) in 8-bit fixed point: all the backward needs of it
-    g = ops.gemm_nt(act, h2, cache.get(wfc, "n"), ops.empty((M, Fd), BF16, x), bias=bfc, aux=f)  # act: erf GELU or QuickGELU epilogue
-    y = ops.gemm_nt(epi_res, g, cache.get(wproj, "n"), ops.empty((M, C), x.dtype, x), bias=bproj, resid=xmid)
-    return y, (mean1, rstd1, h1, qkv, a, lse, xmid, mean2, rstd2, h2, f, g)
+    g = ops.gemm_nt(act, h2, cache.get(p.wfc, "n"), ops.empty((M, Fd), BF16, x), bias=p.bfc, aux=f)  # act: erf GELU or QuickGELU epilogue
+    y = ops.gemm_nt(epi_res, g, cache.get(p.wproj, "n"), ops.empty((M, C), x.dtype, x), bias=p.bproj, resid=xmid)
+    return y, _BlockSaved(mean1, rstd1, h1, qkv, a, lse, xmid, mean2, rstd2, h2, f, g)
 
 
 class _BlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj, cache, B, L, heads, causal, recompute,
+    def forward(ctx, x, ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj, ex, B, L, heads, causal, recompute,
                 seq_off=None, act=ops.EPI_BIAS_GELU):
-        p = (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj)
-        y, saved = _block_forward(x, p, cache, B, L, heads, causal, seq_off, act)
-        ctx.meta = (cache, B, L, heads, causal, recompute, seq_off, act)
-        if recompute:  # block-granular activation recompute (transformer.py:579-581): keep only the block input
-            ctx.save_for_backward(x, *p)
-        else:
-            ctx.save_for_backward(x, *p, *saved)
+        p = _BlockParams(ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj)
+        y, saved = _block_forward(x, p, ex, B, L, heads, causal, seq_off, act)
+        ctx.meta = _BlockMeta(ex, B, L, heads, causal, recompute, seq_off, act)
+        # block-granular activation recompute (transformer.py:579-581): keep only the block input
+        ctx.save_for_backward(x, *p, *(() if recompute else saved))
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        cache, B, L, heads, causal, recompute, seq_off, act = ctx.meta
+        m = ctx.meta
+        ex, cache, B, L, heads, causal, seq_off = m.ex, m.ex.cache, m.B, m.L, m.heads, m.causal, m.seq_off
         t = ctx.saved_tensors
-        x, p = t[0], t[1:13]
-        (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj) = p
-        if recompute:
-            _, saved = _block_forward(x, p, cache, B, L, heads, causal, seq_off, act)
-        else:
-            saved = t[13:]
-        (mean1, rstd1, h1, qkv, a, lse, xmid, mean2, rstd2, h2, f, g) = saved
+        x, p = t[0], _BlockParams(*t[1:13])
+        s = _block_forward(x, p, ex, B, L, heads, causal, seq_off, m.act)[1] if m.recompute else _BlockSaved(*t[13:])
         M, C = x.shape
-        Fd = wfc.shape[0]
-        bf = x.dtype == BF16  # bf16 residual stream: dy IS the bf16 GEMM operand; the residual path adds it in bf16 (or from its fp32 companion)
-        keep32 = bf and cache.stream == "bf16-fp32grad"
-        dy_colsum = _take_colsum(dy)  # only the head publishes one (B rows: free): the LAST block's c_proj bias gradient as an fp32 column sum
-        if bf:
-            dy16 = dy.contiguous()
-            dy = (_take_f32(dy) if keep32 else None)
-            dy = dy16 if dy is None else dy
-        else:
-            dy16 = _take_twin(dy, cache)
-            dy = dy.contiguous()
+        Fd = p.wfc.shape[0]
+        dy16, dy, dy_colsum, want_f32 = _take_grad(dy, x, ex)
         # one zeroed fp32 arena for all of the block's parameter gradients (wgrad kernels accumulate atomically)
-        grads = _grad_arena(p)
-        (dln1w, dln1b, dwqkv, dbqkv, dwo, dbo, dln2w, dln2b, dwfc, dbfc, dwproj, dbproj) = grads
+        d = _grad_arena(p)
         # (Round 4 tried ALL c_proj / out_proj bias gradients as fp32 column sums taken inside the LayerNorm backward that produces dy / dxmid
         # (``dcol``): on all rows it costs that kernel 3-4 % (0.5 ms per step) and moves no digit of the parity report -- the bias gradients'
         # error at batch 4096 was a same-sign error of the summands, loss.py -- so the blocks keep the weight-gradient GEMM's own bias row.)
         if dy_colsum is not None:
-            dbproj.copy_(dy_colsum)
+            d.bproj.copy_(dy_colsum)
 
         dev = x.device
         # a locked block (lock_image_tower / lock_text_tower with some groups left trainable above it) still has to pass the gradient
@@ -291,36 +317,29 @@ class _BlockFn(torch.autograd.Function):
         # always wanted; the four weight-gradient GEMMs are skipped when none of the block's parameters trains
         need_w = any(ctx.needs_input_grad[1:13])
         # ---- MLP branch: x_out = x_mid + c_proj(gelu(c_fc(ln_2(x_mid)))) ----
-        df = ops.gemm_nt(ops.EPI_DGELU, dy16, cache.get(wproj, "t"), ops.empty((M, Fd), BF16, x), aux=f)
-        dh2 = ops.gemm_nt(ops.EPI_BF16, df, cache.get(wfc, "t"), ops.empty((M, C), BF16, x))
-        pair, det = cache.pair_wgrad, cache.deterministic
+        df = ops.gemm_nt(ops.EPI_DGELU, dy16, cache.get(p.wproj, "t"), ops.empty((M, Fd), BF16, x), aux=s.f)
+        dh2 = ops.gemm_nt(ops.EPI_BF16, df, cache.get(p.wfc, "t"), ops.empty((M, C), BF16, x))
+        pair, det = ex.pair_wgrad, ex.deterministic
         with _Paired(dev, cache, pair) as side:
             if need_w:
-                side(ops.gemm_tn_accum, dy16, g, dwproj, None if dy_colsum is not None else dbproj, 1.0, det)
-            dxmid, dxmid16 = ops.layernorm_bwd(dh2, xmid, ln2w, mean2, rstd2, dln2w, dln2b, dres=dy, want_f32=(not bf or keep32), want_bf16=True, deterministic=cache.deterministic)
+                side(ops.gemm_tn_accum, dy16, s.g, d.wproj, None if dy_colsum is not None else d.bproj, 1.0, det)
+            dxmid, dxmid16 = ops.layernorm_bwd(dh2, s.xmid, p.ln2w, s.mean2, s.rstd2, d.ln2w, d.ln2b, dres=dy, want_f32=want_f32, want_bf16=True, deterministic=det)
         # ---- attention branch: x_mid = x + out_proj(attn(in_proj(ln_1(x)))) ----
-        da = ops.gemm_nt(ops.EPI_BF16, dxmid16, cache.get(wo, "t"), ops.empty((M, C), BF16, x))
+        da = ops.gemm_nt(ops.EPI_BF16, dxmid16, cache.get(p.wo, "t"), ops.empty((M, C), BF16, x))
         with _Paired(dev, cache, pair) as side:
             if need_w:
-                side(ops.gemm_tn_accum, df, h2, dwfc, dbfc, 1.0, det)
-            dqkv = ops.attn_bwd(qkv, a, da, lse, B, L, heads, causal, (C // heads) ** -0.5, C // heads, seq_off)
-        dh1 = ops.gemm_nt(ops.EPI_BF16, dqkv, cache.get(wqkv, "t"), ops.empty((M, C), BF16, x))
+                side(ops.gemm_tn_accum, df, s.h2, d.wfc, d.bfc, 1.0, det)
+            dqkv = ops.attn_bwd(s.qkv, s.a, da, s.lse, B, L, heads, causal, (C // heads) ** -0.5, C // heads, seq_off)
+        dh1 = ops.gemm_nt(ops.EPI_BF16, dqkv, cache.get(p.wqkv, "t"), ops.empty((M, C), BF16, x))
         with _Paired(dev, cache, pair) as side:
             if need_w and det:
-                side(ops.gemm_tn_accum, dxmid16, a, dwo, dbo, 1.0, True)
-                side(ops.gemm_tn_accum, dqkv, h1, dwqkv, dbqkv, 1.0, True)
+                side(ops.gemm_tn_accum, dxmid16, s.a, d.wo, d.bo, 1.0, True)
+                side(ops.gemm_tn_accum, dqkv, s.h1, d.wqkv, d.bqkv, 1.0, True)
             elif need_w:  # out-proj and QKV wgrads share their rows and their K = C: one launch (36 tiles, 7 M-splits instead of 28 + 9)
-                side(ops.gemm_tn_accum2, dxmid16, a, dwo, dbo, dqkv, h1, dwqkv, dbqkv)
-            dx, dx16 = ops.layernorm_bwd(dh1, x, ln1w, mean1, rstd1, dln1w, dln1b, dres=(dxmid if dxmid is not None else dxmid16), want_f32=(not bf or keep32),
-                                         want_bf16=True, deterministic=cache.deterministic)
-        if bf:
-            _publish_f32(dx16, dx)
-            dx = dx16
-        else:
-            _publish_twin(dx, dx16)
-        if not need_w:
-            grads = [None] * 12
-        return (dx, *grads, None, None, None, None, None, None, None, None)
+                side(ops.gemm_tn_accum2, dxmid16, s.a, d.wo, d.bo, dqkv, s.h1, d.wqkv, d.bqkv)
+            dx, dx16 = ops.layernorm_bwd(dh1, x, p.ln1w, s.mean1, s.rstd1, d.ln1w, d.ln1b, dres=(dxmid if dxmid is not None else dxmid16), want_f32=want_f32,
+                                         want_bf16=True, deterministic=det)
+        return _hand_down(ctx, x, dx, dx16, d, need_w)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -338,123 +357,104 @@ class _BlockFn(torch.autograd.Function):
 # the single-query kernel of csrc/attention_pooled.hip (2 L d flops per head instead of 4 L^2 d; dK / dV are rank-1 in every key row), the
 # dgrad below it contracts over 2C instead of 3C, and the pooled rows' share of LayerNorm-1's backward (the query path + the residual) is
 # evaluated on those B rows and enters the all-row LayerNorm backward as its residual-gradient input (LayerNorm's backward is linear in dy).
-def _pooled_block_forward(x, p, rows, cache, B, L, heads, causal, seq_off=None, act=ops.EPI_BIAS_GELU):
-    (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj) = p
+# activations the pooled block keeps for its backward; ``*_p`` live on the B pooled rows.  Of the last seven the all-query form fills ``qkv`` / ``a``
+# and the single-query form the other five (``kv is not None`` tells the forms apart); the rest stay None, which save_for_backward accepts
+_PooledSaved = namedtuple("_PooledSaved", "mean1 rstd1 h1 lse a_p xmid_p mean2 rstd2 h2_p f_p g_p x_p qkv a kv q_p h1_p mean1_p rstd1_p", defaults=(None,) * 7)
+
+
+def _pooled_block_forward(x, p, rows, ex, B, L, heads, causal, seq_off=None, act=ops.EPI_BIAS_GELU):
+    cache = ex.cache
     M, C = x.shape
     hd = C // heads
-    single = cache.single_query and hd == 64
-    h1, _, mean1, rstd1 = ops.layernorm_fwd(x, ln1w, ln1b)
+    h1, _, mean1, rstd1 = ops.layernorm_fwd(x, p.ln1w, p.ln1b)
     x_p = ops.gather_rows(x, rows, B, 0)  # [B, C]: from here on only the pooled rows
-    if single:
-        w_n = cache.get(wqkv, "n")  # [3C, C] bf16, rows [Wq; Wk; Wv] (transformer.py:93-95)
-        kv = ops.gemm_nt(ops.EPI_BF16, h1, w_n[C:], ops.empty((M, 2 * C), BF16, x), bias=bqkv[C:])
-        h1_p, _, mean1_p, rstd1_p = ops.layernorm_fwd(x_p, ln1w, ln1b)  # the pooled rows of h1 (row-wise op: the same values)
-        q_p = ops.gemm_nt(ops.EPI_BF16, h1_p, w_n[:C], ops.empty((B, C), BF16, x), bias=bqkv[:C])
+    if ex.single_query and hd == 64:
+        w_n = cache.get(p.wqkv, "n")  # [3C, C] bf16, rows [Wq; Wk; Wv] (transformer.py:93-95)
+        kv = ops.gemm_nt(ops.EPI_BF16, h1, w_n[C:], ops.empty((M, 2 * C), BF16, x), bias=p.bqkv[C:])
+        h1_p, _, mean1_p, rstd1_p = ops.layernorm_fwd(x_p, p.ln1w, p.ln1b)  # the pooled rows of h1 (row-wise op: the same values)
+        q_p = ops.gemm_nt(ops.EPI_BF16, h1_p, w_n[:C], ops.empty((B, C), BF16, x), bias=p.bqkv[:C])
         a_p, lse = ops.attn_pooled_fwd(q_p, kv, rows, B, L, heads, causal, hd ** -0.5, seq_off)
-        att = (kv, q_p, h1_p, mean1_p, rstd1_p)
+        att = dict(kv=kv, q_p=q_p, h1_p=h1_p, mean1_p=mean1_p, rstd1_p=rstd1_p)
     else:
-        qkv = ops.gemm_nt(ops.EPI_BF16, h1, cache.get(wqkv, "n"), ops.empty((M, 3 * C), BF16, x), bias=bqkv)
+        qkv = ops.gemm_nt(ops.EPI_BF16, h1, cache.get(p.wqkv, "n"), ops.empty((M, 3 * C), BF16, x), bias=p.bqkv)
         a, lse = ops.attn_fwd(qkv, B, L, heads, causal, hd ** -0.5, hd, seq_off)
         a_p = ops.gather_rows_bf16(a, rows, B, 0)
-        att = (qkv, a)
-    xmid_p = ops.gemm_nt(ops.EPI_BIAS_RESID_F32, a_p, cache.get(wo, "n"), ops.empty((B, C), F32, x), bias=bo, resid=x_p)
-    h2_p, _, mean2, rstd2 = ops.layernorm_fwd(xmid_p, ln2w, ln2b)
-    Fd = wfc.shape[0]
+        att = dict(qkv=qkv, a=a)
+    xmid_p = ops.gemm_nt(ops.EPI_BIAS_RESID_F32, a_p, cache.get(p.wo, "n"), ops.empty((B, C), F32, x), bias=p.bo, resid=x_p)
+    h2_p, _, mean2, rstd2 = ops.layernorm_fwd(xmid_p, p.ln2w, p.ln2b)
+    Fd = p.wfc.shape[0]
     f_p = ops.empty((B, Fd), torch.uint8, x)
-    g_p = ops.gemm_nt(act, h2_p, cache.get(wfc, "n"), ops.empty((B, Fd), BF16, x), bias=bfc, aux=f_p)
-    y_p = ops.gemm_nt(ops.EPI_BIAS_RESID_F32, g_p, cache.get(wproj, "n"), ops.empty((B, C), F32, x), bias=bproj, resid=xmid_p)
-    return y_p, (mean1, rstd1, h1, lse, a_p, xmid_p, mean2, rstd2, h2_p, f_p, g_p, x_p, *att)
+    g_p = ops.gemm_nt(act, h2_p, cache.get(p.wfc, "n"), ops.empty((B, Fd), BF16, x), bias=p.bfc, aux=f_p)
+    y_p = ops.gemm_nt(ops.EPI_BIAS_RESID_F32, g_p, cache.get(p.wproj, "n"), ops.empty((B, C), F32, x), bias=p.bproj, resid=xmid_p)
+    return y_p, _PooledSaved(mean1, rstd1, h1, lse, a_p, xmid_p, mean2, rstd2, h2_p, f_p, g_p, x_p, **att)
 
 
 class _PooledBlockFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj, rows, cache, B, L, heads, causal, recompute,
+    def forward(ctx, x, ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj, rows, ex, B, L, heads, causal, recompute,
                 seq_off=None, act=ops.EPI_BIAS_GELU):
-        p = (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj)
-        y_p, saved = _pooled_block_forward(x, p, rows, cache, B, L, heads, causal, seq_off, act)
-        ctx.meta = (cache, B, L, heads, causal, recompute, seq_off, act)
-        if recompute:
-            ctx.save_for_backward(x, *p, rows)
-        else:
-            ctx.save_for_backward(x, *p, rows, *saved)
+        p = _BlockParams(ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj)
+        y_p, saved = _pooled_block_forward(x, p, rows, ex, B, L, heads, causal, seq_off, act)
+        ctx.meta = _BlockMeta(ex, B, L, heads, causal, recompute, seq_off, act)
+        ctx.save_for_backward(x, *p, rows, *(() if recompute else saved))
         return y_p
 
     @staticmethod
     def backward(ctx, dy_p):
-        cache, B, L, heads, causal, recompute, seq_off, act = ctx.meta
+        m = ctx.meta
+        ex, cache, B, L, heads, causal, seq_off = m.ex, m.ex.cache, m.B, m.L, m.heads, m.causal, m.seq_off
         t = ctx.saved_tensors
-        x, p, rows = t[0], t[1:13], t[13]
-        (ln1w, ln1b, wqkv, bqkv, wo, bo, ln2w, ln2b, wfc, bfc, wproj, bproj) = p
-        saved = _pooled_block_forward(x, p, rows, cache, B, L, heads, causal, seq_off, act)[1] if recompute else t[14:]
-        (mean1, rstd1, h1, lse, a_p, xmid_p, mean2, rstd2, h2_p, f_p, g_p, x_p) = saved[:12]
-        att = saved[12:]
-        single = len(att) == 5  # (kv, q_p, h1_p, mean1_p, rstd1_p) of the single-query form, (qkv, a) otherwise
+        x, p, rows = t[0], _BlockParams(*t[1:13]), t[13]
+        s = _pooled_block_forward(x, p, rows, ex, B, L, heads, causal, seq_off, m.act)[1] if m.recompute else _PooledSaved(*t[14:])
         M, C = x.shape
-        Fd = wfc.shape[0]
+        Fd = p.wfc.shape[0]
         hd = C // heads
-        dy16 = _take_twin(dy_p, cache)
-        dy_colsum = _take_colsum(dy_p)
-        dy_p = dy_p.contiguous()
-        grads = _grad_arena(p)
-        (dln1w, dln1b, dwqkv, dbqkv, dwo, dbo, dln2w, dln2b, dwfc, dbfc, dwproj, dbproj) = grads
+        det = ex.deterministic
+        dy16, dy_p, dy_colsum, want_f32 = _take_grad(dy_p, x, ex)  # this block's output, and so dy_p, is fp32 on either stream; x is the stream's
+        d = _grad_arena(p)
         need_w = any(ctx.needs_input_grad[1:13])
         # ---- MLP branch and out-projection: the B pooled rows (the same arithmetic as the full block's, row for row) ----
         if dy_colsum is not None:
-            dbproj.copy_(dy_colsum)
+            d.bproj.copy_(dy_colsum)
         else:
-            ops.colsum_f32(dy_p, dbproj, cache.deterministic)
-        df_p = ops.gemm_nt(ops.EPI_DGELU, dy16, cache.get(wproj, "t"), ops.empty((B, Fd), BF16, x), aux=f_p)
-        dh2_p = ops.gemm_nt(ops.EPI_BF16, df_p, cache.get(wfc, "t"), ops.empty((B, C), BF16, x))
-        dxmid_p, dxmid16_p = ops.layernorm_bwd(dh2_p, xmid_p, ln2w, mean2, rstd2, dln2w, dln2b, dres=dy_p, want_f32=True, want_bf16=True, deterministic=cache.deterministic)
-        det = cache.deterministic
+            ops.colsum_f32(dy_p, d.bproj, det)
+        df_p = ops.gemm_nt(ops.EPI_DGELU, dy16, cache.get(p.wproj, "t"), ops.empty((B, Fd), BF16, x), aux=s.f_p)
+        dh2_p = ops.gemm_nt(ops.EPI_BF16, df_p, cache.get(p.wfc, "t"), ops.empty((B, C), BF16, x))
+        dxmid_p, dxmid16_p = ops.layernorm_bwd(dh2_p, s.xmid_p, p.ln2w, s.mean2, s.rstd2, d.ln2w, d.ln2b, dres=dy_p, want_f32=True, want_bf16=True, deterministic=det)
         if need_w:
-            ops.gemm_tn_accum(dy16, g_p, dwproj, None, 1.0, det)
-            ops.gemm_tn_accum(df_p, h2_p, dwfc, dbfc, 1.0, det)
-            ops.gemm_tn_accum(dxmid16_p, a_p, dwo, dbo, 1.0, det)
+            ops.gemm_tn_accum(dy16, s.g_p, d.wproj, None, 1.0, det)
+            ops.gemm_tn_accum(df_p, s.h2_p, d.wfc, d.bfc, 1.0, det)
+            ops.gemm_tn_accum(dxmid16_p, s.a_p, d.wo, d.bo, 1.0, det)
         # what reaches x besides LayerNorm-1's all-row backward lives on the B pooled rows only: it is ADDED into those rows of dx behind that kernel
         # (ocn_scatter_add_rows) instead of travelling through a zero [M, C] fp32 residual-gradient matrix (1 GB of fills and reads per step)
-        if single:
-            kv, q_p, h1_p, mean1_p, rstd1_p = att
-            w_t = cache.get(wqkv, "t")  # [C, 3C] bf16: columns [Wq^T | Wk^T | Wv^T]
-            da_p = ops.gemm_nt(ops.EPI_BF16, dxmid16_p, cache.get(wo, "t"), ops.empty((B, C), BF16, x))
-            dq_p, dkv = ops.attn_pooled_bwd(q_p, kv, a_p, da_p, lse, rows, B, L, heads, causal, hd ** -0.5, seq_off)
+        if s.kv is not None:  # single-query form
+            w_t = cache.get(p.wqkv, "t")  # [C, 3C] bf16: columns [Wq^T | Wk^T | Wv^T]
+            da_p = ops.gemm_nt(ops.EPI_BF16, dxmid16_p, cache.get(p.wo, "t"), ops.empty((B, C), BF16, x))
+            dq_p, dkv = ops.attn_pooled_bwd(s.q_p, s.kv, s.a_p, da_p, s.lse, rows, B, L, heads, causal, hd ** -0.5, seq_off)
             dh1 = ops.gemm_nt(ops.EPI_BF16, dkv, w_t[:, C:], ops.empty((M, C), BF16, x))       # every row: through K and V
             dh1q_p = ops.gemm_nt(ops.EPI_F32, dq_p, w_t[:, :C], ops.empty((B, C), F32, x))     # the pooled rows: through their query
             if need_w:
-                ops.gemm_tn_accum(dkv, h1, dwqkv[C:], dbqkv[C:], 1.0, det)
-                ops.gemm_tn_accum(dq_p, h1_p, dwqkv[:C], dbqkv[:C], 1.0, det)
+                ops.gemm_tn_accum(dkv, s.h1, d.wqkv[C:], d.bqkv[C:], 1.0, det)
+                ops.gemm_tn_accum(dq_p, s.h1_p, d.wqkv[:C], d.bqkv[:C], 1.0, det)
             # pooled rows: LayerNorm-1 backward of the query path + the residual x -> xmid
-            dxp, _ = ops.layernorm_bwd(dh1q_p, x_p, ln1w, mean1_p, rstd1_p, dln1w, dln1b, dres=dxmid_p, want_f32=True, want_bf16=False, deterministic=cache.deterministic)
-        else:
-            qkv, a = att
-            # ---- attention and everything below it: every row (the pooled rows' queries read all keys / values) ----
-            da_p = ops.gemm_nt(ops.EPI_F32, dxmid16_p, cache.get(wo, "t"), ops.empty((B, C), F32, x))
-            da = torch.zeros((M, C), dtype=BF16, device=x.device)
-            ops.scatter_rows(da_p, rows, None, B, 0, da)
-            dqkv = ops.attn_bwd(qkv, a, da, lse, B, L, heads, causal, hd ** -0.5, hd, seq_off)
-            dh1 = ops.gemm_nt(ops.EPI_BF16, dqkv, cache.get(wqkv, "t"), ops.empty((M, C), BF16, x))
-            if need_w:
-                ops.gemm_tn_accum(dqkv, h1, dwqkv, dbqkv, 1.0, det)
-            dxp = None
-        bf = x.dtype == BF16  # bf16 residual stream below this block: its input gradient leaves as bf16 (see _BlockFn.backward)
-        keep32 = bf and cache.stream == "bf16-fp32grad"
-        if dxp is not None:
-            dx, dx16 = ops.layernorm_bwd(dh1, x, ln1w, mean1, rstd1, dln1w, dln1b, want_f32=(not bf or keep32), want_bf16=True, deterministic=cache.deterministic)
+            dxp, _ = ops.layernorm_bwd(dh1q_p, s.x_p, p.ln1w, s.mean1_p, s.rstd1_p, d.ln1w, d.ln1b, dres=dxmid_p, want_f32=True, want_bf16=False, deterministic=det)
+            dx, dx16 = ops.layernorm_bwd(dh1, x, p.ln1w, s.mean1, s.rstd1, d.ln1w, d.ln1b, want_f32=want_f32, want_bf16=True, deterministic=det)
             ops.scatter_add_rows(dxp, rows, dx, B, 0, dx16)
         else:
+            # ---- attention and everything below it: every row (the pooled rows' queries read all keys / values) ----
+            da_p = ops.gemm_nt(ops.EPI_F32, dxmid16_p, cache.get(p.wo, "t"), ops.empty((B, C), F32, x))
+            da = torch.zeros((M, C), dtype=BF16, device=x.device)
+            ops.scatter_rows(da_p, rows, None, B, 0, da)
+            dqkv = ops.attn_bwd(s.qkv, s.a, da, s.lse, B, L, heads, causal, hd ** -0.5, hd, seq_off)
+            dh1 = ops.gemm_nt(ops.EPI_BF16, dqkv, cache.get(p.wqkv, "t"), ops.empty((M, C), BF16, x))
+            if need_w:
+                ops.gemm_tn_accum(dqkv, s.h1, d.wqkv, d.bqkv, 1.0, det)
             # the all-query form keeps the full block's arithmetic to the bit (the residual gradient enters INSIDE the LayerNorm backward, where the
             # compiler contracts it into an FMA): it is the form tests/test_model_gpu.py::test_pooled_last_block_equals_full_block proves exact
             dres = torch.zeros((M, C), dtype=F32, device=x.device)
             ops.scatter_rows(dxmid_p, rows, dres, B, 0, None)  # the residual path x -> xmid carries gradient on the pooled rows only
-            dx, dx16 = ops.layernorm_bwd(dh1, x, ln1w, mean1, rstd1, dln1w, dln1b, dres=dres, want_f32=(not bf or keep32), want_bf16=True, deterministic=cache.deterministic)
-        if bf:
-            _publish_f32(dx16, dx)
-            dx = dx16
-        else:
-            _publish_twin(dx, dx16)
-        if not need_w:
-            grads = [None] * 12
-        return (dx, *grads, None, None, None, None, None, None, None, None, None)
+            dx, dx16 = ops.layernorm_bwd(dh1, x, p.ln1w, s.mean1, s.rstd1, d.ln1w, d.ln1b, dres=dres, want_f32=want_f32, want_bf16=True, deterministic=det)
+        return _hand_down(ctx, x, dx, dx16, d, need_w)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -462,7 +462,8 @@ class _PooledBlockFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------
 class _VisionEmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image, conv_w, cls, pos, lnw, lnb, cache, patch, norm=None):
+    def forward(ctx, image, conv_w, cls, pos, lnw, lnb, ex, patch, norm=None):
+        cache = ex.cache
         width = conv_w.shape[0]
         KP = 3 * patch * patch
         Kpad = _round_up(KP, 64)
@@ -482,12 +483,12 @@ class _VisionEmbedFn(torch.autograd.Function):
             w16[:, :KP].copy_(cache.get(conv_w, "n"))
         po = ops.gemm_nt(ops.EPI_F32, patches, w16, ops.empty((B * G, width), F32, patches))
         emb = ops.embed_assemble_fwd(po, cls, pos, B, G, width)
-        bf = cache.stream != "fp32"  # bf16 residual stream: ln_pre hands its result on in bf16 (layers.py:23-26 under autocast); emb itself stays fp32 here
+        bf = ex.stream != "fp32"  # bf16 residual stream: ln_pre hands its result on in bf16 (layers.py:23-26 under autocast); emb itself stays fp32 here
         x16, x0, mean, rstd = ops.layernorm_fwd(emb, lnw, lnb, want_bf16=bf, want_f32=not bf)
         x0 = x16 if bf else x0
         ctx.save_for_backward(patches, emb, mean, rstd, lnw, conv_w, cls, pos)
         ctx.meta = (B, G, width, KP, Kpad)
-        ctx.cache = cache
+        ctx.det = ex.deterministic
         return x0
 
     @staticmethod
@@ -498,11 +499,11 @@ class _VisionEmbedFn(torch.autograd.Function):
         dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
         dy0 = (_take_f32(dx0) if dx0.dtype == BF16 else None)  # bf16 stream: the first block's fp32 companion when there is one
         dy0 = dx0.contiguous() if dy0 is None else dy0
-        demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.cache.deterministic)
+        demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.det)
         dpos, dcls = torch.zeros_like(pos), torch.zeros_like(cls)
-        dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.cache.deterministic)
+        dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det)
         dw = torch.zeros(width, Kpad, dtype=F32, device=dev)
-        ops.gemm_tn_accum(dpatch, patches, dw, None, 1.0, ctx.cache.deterministic)
+        ops.gemm_tn_accum(dpatch, patches, dw, None, 1.0, ctx.det)
         dconv = (dw if Kpad == KP else dw[:, :KP].contiguous()).view(conv_w.shape)
         return None, dconv, dcls, dpos, dlnw, dlnb, None, None, None
 
@@ -512,13 +513,13 @@ class _VisionEmbedFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------
 class _TextEmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, text, table, pos, pack=None, deterministic=False):
+    def forward(ctx, text, table, pos, pack, ex):
         if pack is None:
             x = ops.token_embed_fwd(text.contiguous(), table, pos)
         else:
             x = ops.token_embed_fwd_rows(pack.tokens, pack.posidx, table, pos)
         ctx.pack = pack
-        ctx.det = bool(deterministic)
+        ctx.det = ex.deterministic
         ctx.save_for_backward(text, table, pos)
         return x
 
@@ -590,43 +591,45 @@ class _TextPack:
 # ------------------------------------------------------------------------------------------------------
 class _HeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, lnw, lnb, proj, idx, cache, B, L, normalize):
-        pooled = ops.gather_rows(x, idx, B, L)
+    def forward(ctx, x, lnw, lnb, proj, rows, ex, B, normalize):
+        """``rows`` (int32 [B]): absolute row of each sequence's pooled token in ``x``"""
+        pooled = ops.gather_rows(x, rows, B, 0)
         p16, _, mean, rstd = ops.layernorm_fwd(pooled, lnw, lnb)
         E = proj.shape[1]
-        feat = ops.gemm_nt(ops.EPI_F32, p16, cache.get(proj, "t"), ops.empty((B, E), F32, x))
+        feat = ops.gemm_nt(ops.EPI_F32, p16, ex.cache.get(proj, "t"), ops.empty((B, E), F32, x))
         if normalize:
             y, _, inv = ops.l2norm_fwd(feat)
         else:
             y, inv = feat, None
-        ctx.save_for_backward(pooled, p16, mean, rstd, lnw, proj, idx, y, inv)
-        ctx.meta = (cache, B, L, normalize, x.shape, x.dtype)
+        ctx.save_for_backward(pooled, p16, mean, rstd, lnw, proj, rows, y, inv)
+        ctx.meta = (ex, B, normalize, x.shape, x.dtype)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        pooled, p16, mean, rstd, lnw, proj, idx, y, inv = ctx.saved_tensors
-        cache, B, L, normalize, xshape, xdtype = ctx.meta
+        pooled, p16, mean, rstd, lnw, proj, rows, y, inv = ctx.saved_tensors
+        ex, B, normalize, xshape, xdtype = ctx.meta
+        none = [None] * (len(ctx.needs_input_grad) - 4)
         dy = dy.contiguous().float()
         dfeat = ops.l2norm_bwd(dy, y, inv) if normalize else dy
         dfeat16 = ops.cast_bf16(dfeat)
         C, E = proj.shape
         # fp32 into the LayerNorm backward (B rows: free): ln_post / ln_final's bias gradient is a column sum over the B pooled rows
-        dp32 = ops.gemm_nt(ops.EPI_F32, dfeat16, cache.get(proj, "n"), ops.empty((B, C), F32, dy))
+        dp32 = ops.gemm_nt(ops.EPI_F32, dfeat16, ex.cache.get(proj, "n"), ops.empty((B, C), F32, dy))
         dproj = torch.zeros_like(proj)
-        ops.gemm_tn_accum(p16, dfeat16, dproj, None, 1.0, cache.deterministic)
+        ops.gemm_tn_accum(p16, dfeat16, dproj, None, 1.0, ex.deterministic)
         dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
         dcol = torch.zeros_like(lnw)  # column sums of dpooled = of dx (zero elsewhere): the last block's c_proj bias gradient, in fp32
-        dpooled, _ = ops.layernorm_bwd(dp32, pooled, lnw, mean, rstd, dlnw, dlnb, want_f32=True, dcol=dcol, deterministic=cache.deterministic)
+        dpooled, _ = ops.layernorm_bwd(dp32, pooled, lnw, mean, rstd, dlnw, dlnb, want_f32=True, dcol=dcol, deterministic=ex.deterministic)
         dx16 = torch.zeros(xshape, dtype=BF16, device=dy.device)  # bf16 twin for the last block's dgrad / wgrad GEMMs
         if xdtype == BF16:  # all rows of a bf16 residual stream (full last block): the gradient itself is the bf16 tensor
-            ops.scatter_rows(dpooled, idx, None, B, L, dx16)
+            ops.scatter_rows(dpooled, rows, None, B, 0, dx16)
             _publish_f32(dx16, None, dcol)
-            return dx16, dlnw, dlnb, dproj, None, None, None, None, None
+            return (dx16, dlnw, dlnb, dproj, *none)
         dx = torch.zeros(xshape, dtype=F32, device=dy.device)
-        ops.scatter_rows(dpooled, idx, dx, B, L, dx16)
+        ops.scatter_rows(dpooled, rows, dx, B, 0, dx16)
         _publish_twin(dx, dx16, dcol)
-        return dx, dlnw, dlnb, dproj, None, None, None, None, None
+        return (dx, dlnw, dlnb, dproj, *none)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -734,20 +737,20 @@ class ResidualAttentionBlock(nn.Module):  # transformer.py:274-330
         self.act_epilogue = ops.EPI_BIAS_QUICKGELU if quick_gelu else ops.EPI_BIAS_GELU
 
     def params(self):
-        return (self.ln_1.weight, self.ln_1.bias, self.attn.in_proj_weight, self.attn.in_proj_bias,
-                self.attn.out_proj.weight, self.attn.out_proj.bias, self.ln_2.weight, self.ln_2.bias,
-                self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight, self.mlp.c_proj.bias)
+        return _BlockParams(self.ln_1.weight, self.ln_1.bias, self.attn.in_proj_weight, self.attn.in_proj_bias,
+                            self.attn.out_proj.weight, self.attn.out_proj.bias, self.ln_2.weight, self.ln_2.bias,
+                            self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight, self.mlp.c_proj.bias)
 
     def get_weight_dtype(self):
         return self.mlp.c_fc.weight.dtype
 
-    def forward(self, x, cache, B, L, causal, recompute=False, seq_off=None, pooled_rows=None):
+    def forward(self, x, ex, B, L, causal, recompute=False, seq_off=None, pooled_rows=None):
         """``pooled_rows`` (int32 [B], absolute rows): the caller reads only these rows of the output -- everything behind the attention
         then runs on them alone and the result is [B, C] (_PooledBlockFn).  Both forms go through ``Module.__call__``, so forward /
         forward-pre hooks on the block (FSDP2's unshard, feature extraction, profilers) fire either way."""
         if pooled_rows is not None:
-            return _PooledBlockFn.apply(x, *self.params(), pooled_rows, cache, B, L, self.n_head, causal, recompute, seq_off, self.act_epilogue)
-        return _BlockFn.apply(x, *self.params(), cache, B, L, self.n_head, causal, recompute, seq_off, self.act_epilogue)
+            return _PooledBlockFn.apply(x, *self.params(), pooled_rows, ex, B, L, self.n_head, causal, recompute, seq_off, self.act_epilogue)
+        return _BlockFn.apply(x, *self.params(), ex, B, L, self.n_head, causal, recompute, seq_off, self.act_epilogue)
 
 
 class Transformer(nn.Module):  # transformer.py:476-585
@@ -769,7 +772,7 @@ class Transformer(nn.Module):  # transformer.py:476-585
         self.grad_checkpointing = enable
         self.keep_last_blocks = max(0, int(keep_last))
 
-    def forward(self, x, cache, B, L, causal, seq_off=None, pooled_rows=None):
+    def forward(self, x, ex, B, L, causal, seq_off=None, pooled_rows=None):
         """``pooled_rows`` (int32 [B], absolute rows): the caller only reads these rows of the output -- the last block then runs as
         _PooledBlockFn and the result is [B, C] (the pooled rows, in order) instead of [M, C]"""
         rc = self.grad_checkpointing and torch.is_grad_enabled()
@@ -777,15 +780,27 @@ class Transformer(nn.Module):  # transformer.py:476-585
         first_kept = len(blocks) - (self.keep_last_blocks if rc else 0)  # blocks from here on keep their activations
         last = blocks.pop() if pooled_rows is not None else None
         for i, r in enumerate(blocks):
-            x = r(x, cache, B, L, causal, rc and i < first_kept, seq_off)
+            x = r(x, ex, B, L, causal, rc and i < first_kept, seq_off)
         if last is not None:
-            x = last(x, cache, B, L, causal, rc and len(blocks) < first_kept, seq_off, pooled_rows)
+            x = last(x, ex, B, L, causal, rc and len(blocks) < first_kept, seq_off, pooled_rows)
         return x
 
 
 def _pooled_last_block_ok(module) -> bool:
     """the pooled form of the last block (see _PooledBlockFn) unless switched off on the module"""
     return bool(getattr(module, "pooled_last_block", True))
+
+
+def _tower_features(transformer, x, ex, B, L, causal, seq_off, rows, seq, pooled, ln, proj, normalize):
+    """the residual blocks of a tower and its pooled head (_HeadFn).  ``rows`` (int32 [B]): absolute row of each sequence's pooled token in ``x``;
+    ``pooled``: the last block runs behind its attention on those rows alone and hands on [B, C] -- sequence b in row b (``seq`` = arange(B), or None:
+    made here) -- instead of [M, C], where the head gathers ``rows`` itself"""
+    if pooled:
+        x = transformer(x, ex, B, L, causal, seq_off, rows)
+        rows = seq if seq is not None else torch.arange(B, device=x.device, dtype=torch.int32)
+    else:
+        x = transformer(x, ex, B, L, causal, seq_off)
+    return _HeadFn.apply(x, ln.weight, ln.bias, proj, rows, ex, B, normalize)
 
 
 def _set_group_requires_grad(members, requires_grad: bool):  # transformer.py:2034-2041
@@ -863,10 +878,11 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
     def lock(self, unlocked_groups=0, freeze_bn_stats=False):  # transformer.py:745-753
         _lock_layer_groups(self.layer_groups(), unlocked_groups)
 
-    def forward(self, image, normalize=False):
+    def forward(self, image, normalize=False, ex=None):
         """``image``: float [B,3,H,W] (already normalised, as the reference's transform produces) or uint8 pixels
         ([B,3,H,W], or [B,H,W,3] as decoders emit them) which are normalised with ``image_mean`` / ``image_std`` in the
-        patch kernel."""
+        patch kernel.  ``ex``: the _Exec of this call (NativeCLIP.encode_image passes the model's switches; default: _Exec's own defaults)."""
+        ex = ex if ex is not None else _Exec(self._cache)
         B = image.shape[0]
         norm = None
         if image.dtype == torch.uint8:
@@ -879,13 +895,10 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
             raise RuntimeError(f"image size {hw} != {self.image_size}")
         T = self.grid_size[0] * self.grid_size[1] + 1
         x = _VisionEmbedFn.apply(image, self.conv1.weight, self.class_embedding, self.positional_embedding,
-                                 self.ln_pre.weight, self.ln_pre.bias, self._cache, self.patch_size[0], norm)
-        if _pooled_last_block_ok(self):
-            rows = torch.arange(B, device=x.device, dtype=torch.int32)
-            x = self.transformer(x, self._cache, B, T, False, None, rows * T)  # the class token's rows; the result is [B, C]
-            return _HeadFn.apply(x, self.ln_post.weight, self.ln_post.bias, self.proj, rows, self._cache, B, 0, normalize)
-        x = self.transformer(x, self._cache, B, T, False)
-        return _HeadFn.apply(x, self.ln_post.weight, self.ln_post.bias, self.proj, None, self._cache, B, T, normalize)
+                                 self.ln_pre.weight, self.ln_pre.bias, ex, self.patch_size[0], norm)
+        seq = torch.arange(B, device=x.device, dtype=torch.int32)
+        rows = seq * T  # the class token of every image
+        return _tower_features(self.transformer, x, ex, B, T, False, None, rows, seq, _pooled_last_block_ok(self), self.ln_post, self.proj, normalize)
 
 
 ATTENTION_HEAD_DIMS = (64, 80, 88, 96, 104, 112, 128)  # instantiations of csrc/attention_generic.hip (64 also: csrc/attention.hip)
@@ -933,8 +946,10 @@ class NativeCLIP(nn.Module):
         pooled rows only (_PooledBlockFn; ``model.visual.pooled_last_block`` is the image tower's switch); ``attn_buckets`` -- packed
         attention launches grouped by 32-row block count; ``pair_wgrad`` -- in one-stream mode, the blocks' wgrad GEMMs on a side
         stream under the HBM-bound kernels; ``deterministic`` -- every weight / bias gradient GEMM in its reproducible form (per-split
-        slabs summed in a fixed order instead of fp32 atomics: 98 % of the gradient elements; the LayerNorm-affine, embedding and
-        scalar-loss reductions still accumulate with fp32 atomics).
+        slabs summed in a fixed order instead of fp32 atomics), and with it the LayerNorm dgamma / dbeta through per-workgroup slabs, the
+        token-embedding rows by whole runs of a stable sort and the positional / class-embedding gradients by single writers: together with
+        ``NativeClipLoss(deterministic=True)`` no fp32 atomic is left in any sum of the step, and two runs of it give the same bits
+        (tests/test_model_gpu.py::test_deterministic_step_is_bit_reproducible).
         ``image_stream`` DOES change results, inside the stated tolerances: the dtype of the IMAGE tower's residual stream -- "fp32" (default; stricter than
         the reference), "bf16" (stream and its gradient in bf16 = what the reference's autocast produces there, transformer.py:794 + layers.py:23-26;
         half the residual-stream bytes of 24 residual epilogues and 49 LayerNorm passes) or "bf16-fp32grad" (bf16 stream, fp32 residual-gradient path)."""
@@ -1071,46 +1086,33 @@ class NativeCLIP(nn.Module):
     def no_weight_decay(self):
         return {"positional_embedding"} | {"visual." + n for n in self.visual.no_weight_decay()}
 
-    def _sync_options(self, overlap=False):
-        """execution switches of the model onto the two towers' operand caches (which the autograd Functions carry)"""
-        self._cache.pair_wgrad = self.visual._cache.pair_wgrad = self.pair_wgrad and not overlap
-        self._cache.deterministic = self.visual._cache.deterministic = self.deterministic
-        self._cache.single_query = self.visual._cache.single_query = bool(self.pooled_single_query)
-        self.visual._cache.stream = self.image_stream
+    def _exec_options(self, image_tower: bool, overlap=False):
+        """the execution switches of the model, as they stand now, for one call of one tower (_Exec).  ``overlap``: the towers of this call run on two
+        streams (forward()), which switches the per-block wgrad side streams off (see the note on ``tower_streams`` above _StreamMap)"""
+        return _Exec(self.visual._cache if image_tower else self._cache, self.pair_wgrad and not overlap, self.deterministic,
+                     bool(self.pooled_single_query), self.image_stream if image_tower else "fp32")
 
-    def encode_image(self, image, normalize: bool = False):
-        self._cache.deterministic = self.visual._cache.deterministic = self.deterministic
-        self.visual._cache.single_query = bool(self.pooled_single_query)
-        self.visual._cache.stream = self.image_stream
-        return self.visual(image, normalize)
+    def encode_image(self, image, normalize: bool = False, _overlap=False):
+        return self.visual(image, normalize, self._exec_options(True, _overlap))
 
-    def encode_text(self, text, normalize: bool = False, _pack=None):
+    def encode_text(self, text, normalize: bool = False, _pack=None, _overlap=False):
         B, L = text.shape
         if L != self.context_length:
             raise RuntimeError(f"text length {L} != context_length {self.context_length}")
-        self._cache.deterministic = self.visual._cache.deterministic = self.deterministic
-        self._cache.single_query = bool(self.pooled_single_query)
+        ex = self._exec_options(False, _overlap)
         if self.pack_text:
             pack = (_pack if _pack is not None else _TextPack(text, self.vocab_size, self.attn_buckets)).finish()
-            x = _TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, pack, self.deterministic)
-            if _pooled_last_block_ok(self):
-                x = self.transformer(x, self._cache, B, L, True, pack.layout, pack.last_row)  # [B, C]: the EOT rows
-                rows = torch.arange(B, device=x.device, dtype=torch.int32)
-                return _HeadFn.apply(x, self.ln_final.weight, self.ln_final.bias, self.text_projection, rows, self._cache, B, 0, normalize)
-            x = self.transformer(x, self._cache, B, L, True, pack.layout)
-            # L = 0: last_row holds absolute rows of the packed matrix
-            return _HeadFn.apply(x, self.ln_final.weight, self.ln_final.bias, self.text_projection, pack.last_row, self._cache, B, 0, normalize)
-        # ids outside the vocabulary raise like nn.Embedding (model.py:399); the packed path gets the count with its plan's read-back
-        if int(ops.token_range_check(text.contiguous(), self.vocab_size)) != 0:
-            raise IndexError(f"index out of range in self: token id(s) outside [0, {self.vocab_size}) (token_embedding has {self.vocab_size} rows)")
-        x = _TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, None, self.deterministic)
-        idx = ops.argmax_rows(text.contiguous())
-        if _pooled_last_block_ok(self):
-            rows = torch.arange(B, device=x.device, dtype=torch.int32)
-            x = self.transformer(x, self._cache, B, L, True, None, rows * L + idx)
-            return _HeadFn.apply(x, self.ln_final.weight, self.ln_final.bias, self.text_projection, rows, self._cache, B, 0, normalize)
-        x = self.transformer(x, self._cache, B, L, True)
-        return _HeadFn.apply(x, self.ln_final.weight, self.ln_final.bias, self.text_projection, idx, self._cache, B, L, normalize)
+            x = _TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, pack, ex)
+            seq_off, rows, seq = pack.layout, pack.last_row, None  # the EOT rows of the packed matrix
+        else:
+            # ids outside the vocabulary raise like nn.Embedding (model.py:399); the packed path gets the count with its plan's read-back
+            if int(ops.token_range_check(text.contiguous(), self.vocab_size)) != 0:
+                raise IndexError(f"index out of range in self: token id(s) outside [0, {self.vocab_size}) (token_embedding has {self.vocab_size} rows)")
+            x = _TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, None, ex)
+            idx = ops.argmax_rows(text.contiguous())
+            seq_off, seq = None, torch.arange(B, device=x.device, dtype=torch.int32)
+            rows = seq * L + idx
+        return _tower_features(self.transformer, x, ex, B, L, True, seq_off, rows, seq, _pooled_last_block_ok(self), self.ln_final, self.text_projection, normalize)
 
     def get_logits(self, image, text):
         """model.py:413-420: `logit_scale.exp() * image_features @ text_features.T` (+ logit_bias), and its transpose, through the library's own GEMM like
@@ -1125,7 +1127,6 @@ class NativeCLIP(nn.Module):
         # the packed text layout is planned first: its 4-byte read-back then completes while the image tower is being enqueued
         pack = _TextPack(text, self.vocab_size, self.attn_buckets) if (text is not None and self.pack_text) else None
         overlap = self.tower_streams and image is not None and text is not None
-        self._sync_options(overlap)
         if overlap:
             dev = text.device
             cur = torch.cuda.current_stream(dev)
@@ -1135,12 +1136,12 @@ class NativeCLIP(nn.Module):
             serial = self.tower_streams == "serial"  # one tower at a time, on the same two streams (see _AfterStream)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                image_features = self.encode_image(image, normalize=True)
+                image_features = self.encode_image(image, normalize=True, _overlap=True)
                 if serial and image_features.requires_grad:
                     image_features = _AfterStream.apply(image_features, cur)
             if serial:
                 cur.wait_stream(side)
-            text_features = self.encode_text(text, normalize=True, _pack=pack)
+            text_features = self.encode_text(text, normalize=True, _pack=pack, _overlap=True)
             image.record_stream(side)
             cur.wait_stream(side)
             image_features.record_stream(cur)

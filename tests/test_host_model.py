@@ -232,9 +232,9 @@ def test_execution_switches_are_constructor_arguments_and_copies_start_with_empt
     assert (d.pack_text, d.tower_streams, d.pooled_last_block, d.visual.pooled_last_block, d.attn_buckets, d.pair_wgrad, d.deterministic) == \
         (True, True, True, True, True, True, False)
     d._cache._d[("x", "n")] = (0, (1,), torch.zeros(3))
-    d.visual._cache.deterministic = True
+    d.deterministic = True
     twin = copy.deepcopy(d)
-    assert twin._cache._d == {} and twin.visual._cache._d == {} and twin.visual._cache.deterministic is True
+    assert twin._cache._d == {} and twin.visual._cache._d == {} and twin.deterministic is True
     assert ("x", "n") in d._cache._d  # the original keeps its copies
 
 
@@ -277,6 +277,59 @@ def test_last_block_hooks_fire_in_the_pooled_form(monkeypatch):
     x = torch.randn(10, 64)
     y = t(x, None, 2, 5, False, None, torch.tensor([0, 5], dtype=torch.int32))
     assert fired == ["pre", "post"] and y.shape == (2, 64)
+
+
+def test_direct_encode_calls_run_with_the_models_own_switches(monkeypatch):
+    """the execution switches reach the autograd Functions as one per-call value built from the model's attributes, on every public path:
+    ``encode_image`` on its own honours ``pair_wgrad=False``, and an overlapped ``forward()`` (which runs unpaired) leaves nothing behind for
+    a later stand-alone ``encode_image``.  The kernels are replaced by stand-ins that record the options they are handed."""
+    import open_clip_amd.model as M
+    cfg = get_model_config("tiny-test")
+    width, embed = cfg["vision_cfg"]["width"], cfg["embed_dim"]
+    seen = []
+
+    class FakeEmbed:
+        @staticmethod
+        def apply(image, conv_w, cls, pos, lnw, lnb, ex, patch, norm=None):
+            seen.append(("embed", ex))
+            return torch.zeros(image.shape[0] * pos.shape[0], width)
+
+    class FakeBlock:
+        @staticmethod
+        def apply(x, *a):
+            seen.append(("block", a[12]))
+            return x
+
+    class FakePooled:
+        @staticmethod
+        def apply(x, *a):
+            seen.append(("block", a[13]))
+            return x[a[12].long()]
+
+    class FakeHead:
+        @staticmethod
+        def apply(x, lnw, lnb, proj, rows, ex, B, normalize):
+            seen.append(("head", ex))
+            return torch.zeros(B, embed)
+
+    for name, fake in (("_VisionEmbedFn", FakeEmbed), ("_BlockFn", FakeBlock), ("_PooledBlockFn", FakePooled), ("_HeadFn", FakeHead)):
+        monkeypatch.setattr(M, name, fake)
+    image = torch.zeros(2, 3, *[cfg["vision_cfg"]["image_size"]] * 2)
+    layers = cfg["vision_cfg"]["layers"]
+
+    m = NativeCLIP(cfg["embed_dim"], cfg["vision_cfg"], cfg["text_cfg"], pair_wgrad=False)
+    assert m.encode_image(image).shape == (2, embed)
+    blocks = [ex for kind, ex in seen if kind == "block"]
+    assert len(blocks) == layers and all(ex.pair_wgrad is False for ex in blocks)
+    assert all(ex.cache is m.visual._cache and ex.stream == "fp32" and ex.deterministic is False for _, ex in seen)
+
+    d = NativeCLIP(cfg["embed_dim"], cfg["vision_cfg"], cfg["text_cfg"])
+    assert d._exec_options(True, overlap=True).pair_wgrad is False and d._exec_options(False, overlap=True).pair_wgrad is False
+    del seen[:]
+    d.encode_image(image)
+    blocks = [ex for kind, ex in seen if kind == "block"]
+    assert len(blocks) == layers and all(ex.pair_wgrad is True for ex in blocks)  # nothing stale from the overlapped call's options
+    assert len({ex for _, ex in seen}) == 1  # one value for the whole tower and call
 
 
 def test_partial_recompute_plan():

@@ -67,7 +67,8 @@ int ocn_version(void);
  *   bias [N] fp32 or NULL; resid fp32 [M,ldc] (EPI 2) or bf16 [M,ldc] (EPI 8); aux uint8 [M,ldc] (EPI 1: written, EPI 3: read): the GELU derivative, the only
  *   thing the backward needs of the pre-activation, as q = round((gelu' + 0.13) * 200) in [0, 252] -- gelu' lies in [-0.129, 1.129], so
  *   the decoded value q / 200 - 0.13 is within 0.0025 of it (unbiased; rms 0.0014, what rounding a value in [0.5, 1) to bf16 costs) at
- *   half the bytes of a bf16 copy. */
+ *   half the bytes of a bf16 copy.  Alignment: lda, ldb % 8 == 0; A, B, out, bias and resid on 16 bytes, aux on 8 (checked; operands may be
+ *   views of larger matrices: a row stride and a base pointer are all the kernels take). */
 int ocn_gemm_nt(int epilogue, const void* A, int lda, const void* B, int ldb, void* out, int ldc, int M, int N, int K,
                 const float* bias, const void* resid, void* aux, float alpha, ocn_stream_t stream);
 

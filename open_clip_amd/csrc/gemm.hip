@@ -452,6 +452,10 @@ extern "C" int ocn_gemm_nt(int epilogue, const void* A, int lda, const void* B, 
     OCN_CHECK_ARG(lda >= K && ldb >= K && ldc >= N && lda % 8 == 0 && ldb % 8 == 0, "ocn_gemm_nt: bad leading dims");
     OCN_CHECK_ARG(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0 && ((uintptr_t)out & 15) == 0,
                   "ocn_gemm_nt: operands must be 16-byte aligned");
+    // the epilogues move bias and residual in 16-byte pieces (f32x4 / b128 buffer loads at column multiples of 4 fp32 or 8 bf16) and the saved
+    // derivative in 4- to 16-byte pieces at column multiples of 4 .. 16 of rows that are multiples of 8 bytes apart (ldc % 8 in gemm_nt5.hip)
+    OCN_CHECK_ARG(((uintptr_t)bias & 15) == 0 && ((uintptr_t)resid & 15) == 0 && ((uintptr_t)aux & 7) == 0,
+                  "ocn_gemm_nt: bias and resid must be 16-byte aligned, aux 8-byte aligned");
     OCN_CHECK_ARG((epilogue != OCN_EPI_BIAS_RESID_F32 && epilogue != OCN_EPI_BIAS_RESID_BF16) || resid, "ocn_gemm_nt: residual epilogue needs resid");
     OCN_CHECK_ARG((epilogue != OCN_EPI_BIAS_GELU && epilogue != OCN_EPI_BIAS_QUICKGELU && epilogue != OCN_EPI_DGELU) || aux, "ocn_gemm_nt: gelu epilogues need aux");
     GemmNtArgs a;

@@ -110,6 +110,66 @@ def test_wgrad_sums_the_same_products(held):
                 assert (db0.double() - ref_b).abs().max().item() <= 2e-3 * M ** 0.5
 
 
+_EXACT = {}
+
+
+def _exact_wgrad_cases():
+    """integer operands (tests/gemm_exact.py) of the four wgrad shapes above and of one out-proj / QKV pair, with their exact results: once per module"""
+    from tests import gemm_exact as X
+    if not _EXACT:
+        g = torch.Generator(device=DEV).manual_seed(23)
+        single = []
+        for M, N, K, bias in X.RESCUE_WGRAD_SHAPES:
+            a, b = X.int_operand((M, N), X.R_TN, g, DEV), X.int_operand((M, K), X.R_TN, g, DEV)
+            assert X.R_TN * M < X.LIMIT
+            single.append((a, b, bias, X.f32_exact(X.exact_ref(a, b, "tn")), X.f32_exact(a.double().sum(0))))
+        M, K = 51200, 768
+        a1, a2, b = X.int_operand((M, 768), X.R_TN, g, DEV), X.int_operand((M, 2304), X.R_TN, g, DEV), X.int_operand((M, K), X.R_TN, g, DEV)
+        _EXACT["single"] = single
+        _EXACT["pair"] = (a1, a2, b, [X.f32_exact(X.exact_ref(a, b, "tn")) for a in (a1, a2)], [X.f32_exact(a.double().sum(0)) for a in (a1, a2)])
+    return _EXACT["single"], _EXACT["pair"]
+
+
+@pytest.mark.parametrize("held", [0, 3, 40])
+def test_wgrad_under_rescue_is_exact_on_integer_operands(held):
+    """operands that are small integers (|a|, |b| <= 8: every partial sum an integer below 64 * 51200 < 2^24, exact in fp32 in ANY order of the atomics):
+    dW and dbias of the rescue form under held CUs are bit-equal to the float64 result and to the static form.  A piece of an M-chunk that is added
+    twice (a stale claim) or not at all changes an integer -- which the bound of test_wgrad_sums_the_same_products cannot show."""
+    from tests import gemm_exact as X
+    side, sink = _side()
+    single, (a1, a2, b2, ref2, refb2) = _exact_wgrad_cases()
+    for a, b, bias, ref, ref_b in single:
+        (M, N), K = a.shape, b.shape[1]
+        tag = f"[{M}x{N}x{K}] {held} held"
+        ops.set_tile_rescue(False)
+        dw0, db0 = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
+        ops.gemm_tn_accum(a, b, dw0, db0 if bias else None)
+        X.assert_bit_equal(f"static wgrad {tag}", dw0, ref)
+        ops.set_tile_rescue(True)
+        for rep in range(3):
+            dw, db = torch.zeros(N, K, device=DEV), torch.zeros(N, device=DEV)
+            torch.cuda.synchronize()
+            _occupy(held, 5000, side, sink)
+            ops.gemm_tn_accum(a, b, dw, db if bias else None)
+            torch.cuda.synchronize()
+            X.assert_bit_equal(f"rescue wgrad {tag}, launch {rep}: dW", dw, ref)
+            assert torch.equal(dw, dw0)
+            if bias:
+                X.assert_bit_equal(f"rescue wgrad {tag}, launch {rep}: dbias", db, ref_b)
+                assert torch.equal(db, db0)
+    # one out-proj / QKV pair (ocn_gemm_tn_accum2) under the same conditions
+    M, K = b2.shape
+    ops.set_tile_rescue(True)
+    w1, w2 = torch.zeros(768, K, device=DEV), torch.zeros(2304, K, device=DEV)
+    d1, d2 = torch.zeros(768, device=DEV), torch.zeros(2304, device=DEV)
+    torch.cuda.synchronize()
+    _occupy(held, 5000, side, sink)
+    ops.gemm_tn_accum2(a1, b2, w1, d1, a2, b2, w2, d2)
+    torch.cuda.synchronize()
+    for name, got, want in (("dW1", w1, ref2[0]), ("dW2", w2, ref2[1]), ("dbias1", d1, refb2[0]), ("dbias2", d2, refb2[1])):
+        X.assert_bit_equal(f"paired wgrad under rescue, {held} held: {name}", got, want)
+
+
 def test_paired_wgrads_and_split_k_and_the_fused_loss_under_rescue():
     side, sink = _side()
     g = torch.Generator(device=DEV).manual_seed(13)

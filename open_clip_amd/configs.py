@@ -136,10 +136,19 @@ def get_model_config(name: str) -> dict:
     return cfg
 
 
-def vision_tokens(cfg: dict) -> int:
+def patch_keep_count(num_patches: int, prob: float) -> int:
+    """patches a training step keeps under patch dropout ``prob``: the reference's ``max(1, int(num_tokens * (1 - prob)))`` (transformer.py:47-48)"""
+    if not 0 <= prob < 1:
+        raise ValueError(f"patch_dropout must satisfy 0 <= prob < 1 (got {prob!r})")  # the reference asserts (transformer.py:28)
+    return num_patches if prob == 0 else max(1, int(num_patches * (1 - prob)))
+
+
+def vision_tokens(cfg: dict, patch_dropout=None) -> int:
+    """tokens of the image tower (class token + patches).  ``patch_dropout`` (None / 0: every patch): the tokens a TRAINING step executes with
+    that dropout probability (transformer.py:17-58)"""
     v = cfg["vision_cfg"]
     g = v["image_size"] // v["patch_size"]
-    return g * g + 1
+    return (g * g if not patch_dropout else patch_keep_count(g * g, patch_dropout)) + 1
 
 
 def count_params(cfg: dict) -> int:
@@ -155,18 +164,20 @@ def count_params(cfg: dict) -> int:
     return n
 
 
-def forward_gflops_per_pair(cfg: dict) -> float:
+def forward_gflops_per_pair(cfg: dict, patch_dropout=None) -> float:
     """algorithmic forward GFLOPs (2 x multiply-accumulates) of one image-text pair as the reference executes it (every caption padded to
     context_length): per block and token (4 + 2 r) C^2 multiply-accumulates for QKV, out-projection and the MLP of ratio r, + 2 L C for the
     two attention products; the patch embedding; the two projections.  Reproduces the `gflops` column of the reference's
-    docs/model_profile.csv for all 28 registered configs it lists to 0.1 % (tests/test_reference_dropin.py)."""
+    docs/model_profile.csv for all 28 registered configs it lists to 0.1 % (tests/test_reference_dropin.py).
+    ``patch_dropout`` (None / 0: unchanged): the work a training step EXECUTES when the image tower keeps only ``vision_tokens(cfg, patch_dropout)``
+    tokens, the patch embedding of the kept patches included -- the figure to state MFU on when dropout is on."""
     v, t, e = cfg["vision_cfg"], cfg["text_cfg"], cfg["embed_dim"]
 
     def tower(width, layers, tokens, ratio):
         per_token = (4 + 2 * ratio) * width * width + 2 * tokens * width
         return layers * tokens * per_token
 
-    lv = vision_tokens(cfg)
+    lv = vision_tokens(cfg, patch_dropout)
     macs = tower(v["width"], v["layers"], lv, int(v["width"] * v.get("mlp_ratio", 4.0)) / v["width"])
     macs += (lv - 1) * v["width"] * 3 * v["patch_size"] ** 2 + v["width"] * e
     macs += tower(t["width"], t["layers"], t["context_length"], int(t["width"] * t.get("mlp_ratio", 4.0)) / t["width"]) + t["width"] * e

@@ -6,10 +6,18 @@
 namespace {
 
 // ---- patchify: image [B,3,H,W] -> patches bf16 [B*gh*gw, Kpad], column = c*P*P + i*P + j ------
+// Patch dropout (transformer.py:17-58): with `keep` (int32 [B, K], any order) output row b*K + j is patch keep[b, j] of image b -- the patches a
+// training step drops are never read.  An index outside [0, G) is clamped (as the token kernels clamp ids): no read can leave the image.
+OCN_DEV int kept_patch(const int32_t* __restrict__ keep, long row, int R, int G) {
+    if (!keep) return (int)(row % R);
+    const int g = keep[row];
+    return g < 0 ? 0 : (g >= G ? G - 1 : g);
+}
+
 template <typename T, int VEC>
 __global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ out, int B, int H, int W, int P, int Kpad,
-                                long total) {
-    const int gh = H / P, gw = W / P, KP = 3 * P * P, kv = Kpad / VEC;
+                                long total, const int32_t* __restrict__ keep, int K) {
+    const int gh = H / P, gw = W / P, KP = 3 * P * P, kv = Kpad / VEC, R = keep ? K : gh * gw;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const long row = idx / kv;
         const int k = (int)(idx % kv) * VEC;
@@ -20,7 +28,7 @@ __global__ void patchify_kernel(const T* __restrict__ img, bf16* __restrict__ ou
             continue;
         }
         const int c = k / (P * P), rem = k % (P * P), i = rem / P, j = rem % P;
-        const int b = (int)(row / (gh * gw)), g = (int)(row % (gh * gw)), py = g / gw, px = g % gw;
+        const int b = (int)(row / R), g = kept_patch(keep, row, R, gh * gw), py = g / gw, px = g % gw;
         const T* s = img + (((size_t)b * 3 + c) * H + py * P + i) * W + px * P + j;
 #pragma unroll
         for (int e = 0; e < VEC; ++e) o[e] = f2bf((float)s[e]);
@@ -34,8 +42,8 @@ struct NormC {
     float scale[3], shift[3];  // y = x * scale[c] + shift[c]
 };
 __global__ void patchify_u8_kernel(const unsigned char* __restrict__ img, bf16* __restrict__ out, int B, int H, int W, int P, int Kpad,
-                                   long total, int hwc, NormC nc) {
-    const int gh = H / P, gw = W / P, KP = 3 * P * P, kv = Kpad / 2;
+                                   long total, int hwc, NormC nc, const int32_t* __restrict__ keep, int K) {
+    const int gh = H / P, gw = W / P, KP = 3 * P * P, kv = Kpad / 2, R = keep ? K : gh * gw;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const long row = idx / kv;
         const int k = (int)(idx % kv) * 2;
@@ -46,7 +54,7 @@ __global__ void patchify_u8_kernel(const unsigned char* __restrict__ img, bf16* 
             continue;
         }
         const int c = k / (P * P), rem = k % (P * P), i = rem / P, j = rem % P;
-        const int b = (int)(row / (gh * gw)), g = (int)(row % (gh * gw)), py = g / gw, px = g % gw;
+        const int b = (int)(row / R), g = kept_patch(keep, row, R, gh * gw), py = g / gw, px = g % gw;
         const int y = py * P + i, x = px * P + j;
         float v0, v1;
         if (hwc) {
@@ -68,11 +76,11 @@ __global__ void patchify_u8_kernel(const unsigned char* __restrict__ img, bf16* 
 // stores (8 consecutive k = one colour plane, one patch row, 8 consecutive pixels: bytes 3 apart in the staged row).  The generic
 // kernel above moves 2 bytes in and 4 out per thread (4096 x 224 x 224: 4 ms instead of 0.5).
 __global__ __launch_bounds__(256) void patchify_u8_hwc_kernel(const unsigned char* __restrict__ img, bf16* __restrict__ out, int H, int W, int P,
-                                                              int Kpad, long npatch, NormC nc) {
+                                                              int Kpad, long npatch, NormC nc, const int32_t* __restrict__ keep, int K) {
     extern __shared__ __attribute__((aligned(16))) unsigned char pix[];
-    const int gh = H / P, gw = W / P, rowb = 3 * P, n16 = P * (rowb >> 4), per_row = rowb >> 4, KP = 3 * P * P, nq = Kpad >> 3;
+    const int gh = H / P, gw = W / P, rowb = 3 * P, n16 = P * (rowb >> 4), per_row = rowb >> 4, KP = 3 * P * P, nq = Kpad >> 3, R = keep ? K : gh * gw;
     for (long patch = blockIdx.x; patch < npatch; patch += gridDim.x) {
-        const int b = (int)(patch / (gh * gw)), g = (int)(patch % (gh * gw)), py = g / gw, px = g % gw;
+        const int b = (int)(patch / R), g = kept_patch(keep, patch, R, gh * gw), py = g / gw, px = g % gw;
         const unsigned char* base = img + (((size_t)b * H + (size_t)py * P) * W + (size_t)px * P) * 3;
         __syncthreads();  // the previous patch has been read out of LDS
         for (int t = threadIdx.x; t < n16; t += blockDim.x) {
@@ -485,28 +493,39 @@ int grid_for(long items, int block) {
 
 }  // namespace
 
-extern "C" int ocn_patchify(const void* image, int image_is_bf16, void* patches, int B, int H, int W, int P, int Kpad,
-                            ocn_stream_t stream) {
+static int patchify_impl(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P, int Kpad,
+                         ocn_stream_t stream) {
     OCN_CHECK_ARG(image && patches, "ocn_patchify: null operand");
     OCN_CHECK_ARG(B > 0 && P > 0 && H % P == 0 && W % P == 0 && P % 2 == 0, "ocn_patchify: bad geometry H=%d W=%d P=%d", H, W, P);
     OCN_CHECK_ARG(Kpad >= 3 * P * P && Kpad % 4 == 0, "ocn_patchify: Kpad=%d too small / not a multiple of 4", Kpad);
     hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)B * (H / P) * (W / P);
+    const long rows = (long)B * (keep ? K : (H / P) * (W / P));
     if (P % 4 == 0) {
         const long total = rows * (Kpad / 4);
-        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total);
-        else hipLaunchKernelGGL((patchify_kernel<float, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total);
+        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        else hipLaunchKernelGGL((patchify_kernel<float, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
     } else {
         const long total = rows * (Kpad / 2);
-        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total);
-        else hipLaunchKernelGGL((patchify_kernel<float, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total);
+        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        else hipLaunchKernelGGL((patchify_kernel<float, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
     }
     OCN_CHECK_LAUNCH("ocn_patchify");
     return OCN_OK;
 }
 
-extern "C" int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, void* patches, int B, int H, int W,
-                               int P, int Kpad, ocn_stream_t stream) {
+extern "C" int ocn_patchify(const void* image, int image_is_bf16, void* patches, int B, int H, int W, int P, int Kpad,
+                            ocn_stream_t stream) {
+    return patchify_impl(image, image_is_bf16, nullptr, 0, patches, B, H, W, P, Kpad, stream);
+}
+
+extern "C" int ocn_patchify_keep(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P,
+                                 int Kpad, ocn_stream_t stream) {
+    OCN_CHECK_ARG(keep && K > 0, "ocn_patchify_keep: keep is null or K = %d", K);
+    return patchify_impl(image, image_is_bf16, keep, K, patches, B, H, W, P, Kpad, stream);
+}
+
+static int patchify_u8_impl(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches, int B,
+                            int H, int W, int P, int Kpad, ocn_stream_t stream) {
     OCN_CHECK_ARG(image_u8 && patches && mean3 && std3, "ocn_patchify_u8: null operand");
     OCN_CHECK_ARG(B > 0 && P > 0 && H % P == 0 && W % P == 0 && P % 2 == 0, "ocn_patchify_u8: bad geometry H=%d W=%d P=%d", H, W, P);
     OCN_CHECK_ARG(Kpad >= 3 * P * P && Kpad % 4 == 0, "ocn_patchify_u8: Kpad=%d too small / not a multiple of 4", Kpad);
@@ -517,17 +536,28 @@ extern "C" int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3
         nc.shift[c] = -mean3[c] / std3[c];
     }
     if (hwc && P % 16 == 0 && Kpad % 8 == 0 && ((uintptr_t)image_u8 & 15) == 0 && ((uintptr_t)patches & 15) == 0) {
-        const long npatch = (long)B * (H / P) * (W / P);
+        const long npatch = (long)B * (keep ? K : (H / P) * (W / P));
         hipLaunchKernelGGL(patchify_u8_hwc_kernel, dim3((unsigned)(npatch < 16384 ? npatch : 16384)), dim3(256), 3 * P * P, (hipStream_t)stream,
-                           (const unsigned char*)image_u8, (bf16*)patches, H, W, P, Kpad, npatch, nc);
+                           (const unsigned char*)image_u8, (bf16*)patches, H, W, P, Kpad, npatch, nc, keep, K);
         OCN_CHECK_LAUNCH("ocn_patchify_u8");
         return OCN_OK;
     }
-    const long total = (long)B * (H / P) * (W / P) * (Kpad / 2);
+    const long total = (long)B * (keep ? K : (H / P) * (W / P)) * (Kpad / 2);
     hipLaunchKernelGGL(patchify_u8_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image_u8,
-                       (bf16*)patches, B, H, W, P, Kpad, total, hwc, nc);
+                       (bf16*)patches, B, H, W, P, Kpad, total, hwc, nc, keep, K);
     OCN_CHECK_LAUNCH("ocn_patchify_u8");
     return OCN_OK;
+}
+
+extern "C" int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, void* patches, int B, int H, int W,
+                               int P, int Kpad, ocn_stream_t stream) {
+    return patchify_u8_impl(image_u8, hwc, mean3, std3, nullptr, 0, patches, B, H, W, P, Kpad, stream);
+}
+
+extern "C" int ocn_patchify_u8_keep(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches,
+                                    int B, int H, int W, int P, int Kpad, ocn_stream_t stream) {
+    OCN_CHECK_ARG(keep && K > 0, "ocn_patchify_u8_keep: keep is null or K = %d", K);
+    return patchify_u8_impl(image_u8, hwc, mean3, std3, keep, K, patches, B, H, W, P, Kpad, stream);
 }
 
 extern "C" int ocn_embed_assemble_fwd(const float* patch_out, const float* cls, const float* pos, float* emb, int B, int G,

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .configs import get_model_config
+from .configs import get_model_config, patch_keep_count
 
 F32, BF16 = torch.float32, torch.bfloat16
 
@@ -462,7 +462,10 @@ class _PooledBlockFn(torch.autograd.Function):
 # ------------------------------------------------------------------------------------------------------
 class _VisionEmbedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, image, conv_w, cls, pos, lnw, lnb, ex, patch, norm=None):
+    def forward(ctx, image, conv_w, cls, pos, lnw, lnb, ex, patch, norm=None, keep=None, inv=None):
+        """``keep`` (int32 [B, K], with its inverse ``inv`` [B, G] or None): patch dropout (transformer.py:17-58, :804) -- only those patches of each
+        image are patchified, multiplied and assembled, B * (K + 1) rows go through ln_pre; both are saved, so the backward (and a recomputed
+        block behind it) never draws again"""
         cache = ex.cache
         width = conv_w.shape[0]
         KP = 3 * patch * patch
@@ -471,23 +474,31 @@ class _VisionEmbedFn(torch.autograd.Function):
             mean, std, hwc = norm
             B = image.shape[0]
             H, W = (image.shape[1], image.shape[2]) if hwc else (image.shape[2], image.shape[3])
-            patches = ops.patchify_u8(image.contiguous(), patch, Kpad, mean, std, hwc)
+            patches = ops.patchify_u8(image.contiguous(), patch, Kpad, mean, std, hwc, keep)
         else:
             B, _, H, W = image.shape
-            patches = ops.patchify(image.contiguous(), patch, Kpad)
+            patches = ops.patchify(image.contiguous(), patch, Kpad, keep)
         G = (H // patch) * (W // patch)
+        K = G if keep is None else keep.shape[1]  # patch rows per image
         if Kpad == KP:
             w16 = cache.get(conv_w, "n")
         else:  # zero-padded K (patch 14: 588 -> 640); rare path, weight-sized
             w16 = torch.zeros(width, Kpad, dtype=BF16, device=image.device)
             w16[:, :KP].copy_(cache.get(conv_w, "n"))
-        po = ops.gemm_nt(ops.EPI_F32, patches, w16, ops.empty((B * G, width), F32, patches))
-        emb = ops.embed_assemble_fwd(po, cls, pos, B, G, width)
+        po = ops.gemm_nt(ops.EPI_F32, patches, w16, ops.empty((B * K, width), F32, patches))
+        if keep is None:
+            emb = ops.embed_assemble_fwd(po, cls, pos, B, G, width)
+        else:
+            emb = ops.embed_assemble_keep_fwd(po, cls, pos, keep, B, G, width)
+            ctx.own_plan = inv is not None  # the plan kernel's inv reaches every row of keep; a caller's keep may not be a clean subset
+            if inv is None and any(ctx.needs_input_grad):
+                inv = ops.patch_keep_inverse(keep, G)
         bf = ex.stream != "fp32"  # bf16 residual stream: ln_pre hands its result on in bf16 (layers.py:23-26 under autocast); emb itself stays fp32 here
         x16, x0, mean, rstd = ops.layernorm_fwd(emb, lnw, lnb, want_bf16=bf, want_f32=not bf)
         x0 = x16 if bf else x0
         ctx.save_for_backward(patches, emb, mean, rstd, lnw, conv_w, cls, pos)
         ctx.meta = (B, G, width, KP, Kpad)
+        ctx.keep, ctx.inv = keep, inv
         ctx.det = ex.deterministic
         return x0
 
@@ -501,11 +512,14 @@ class _VisionEmbedFn(torch.autograd.Function):
         dy0 = dx0.contiguous() if dy0 is None else dy0
         demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.det)
         dpos, dcls = torch.zeros_like(pos), torch.zeros_like(cls)
-        dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det)
+        if ctx.keep is None:
+            dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det)
+        else:
+            dpatch = ops.embed_assemble_keep_bwd(demb, ctx.inv, dpos, dcls, B, G, ctx.keep.shape[1], width, ctx.det, zero_dpatch=not ctx.own_plan)
         dw = torch.zeros(width, Kpad, dtype=F32, device=dev)
         ops.gemm_tn_accum(dpatch, patches, dw, None, 1.0, ctx.det)
         dconv = (dw if Kpad == KP else dw[:, :KP].contiguous()).view(conv_w.shape)
-        return None, dconv, dcls, dpos, dlnw, dlnb, None, None, None
+        return None, dconv, dcls, dpos, dlnw, dlnb, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -834,9 +848,40 @@ class _Embedding(_Params):
         self.num_embeddings, self.embedding_dim = vocab, width
 
 
-class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: learnable pos, 'tok' pool, no patch dropout)
-    def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, quick_gelu=False):
+class PatchDropout(nn.Module):  # transformer.py:17-58 (https://arxiv.org/abs/2212.00794)
+    """Holds the setting, no parameters and no arithmetic: in training mode ``VisionTransformer.forward`` draws the kept patches on the device
+    (ops.patch_keep_plan) BEFORE the patch embedding and runs everything on them alone; in eval mode, as in the reference (:33), nothing is dropped.
+    ``last_keep``: the int32 [B, K] plan of the most recent training forward (ascending patch indices per image)."""
+
+    def __init__(self, prob: float = 0.5, exclude_first_token: bool = True):
         super().__init__()
+        if not 0 <= prob < 1:
+            raise ValueError(f"patch_dropout must satisfy 0 <= prob < 1 (got {prob!r})")  # the reference asserts (:28)
+        if not exclude_first_token:
+            raise NotImplementedError("PatchDropout: the class token is always kept (the only form VisionTransformer builds, transformer.py:658)")
+        self.prob = float(prob)
+        self.exclude_first_token = True
+        self.last_keep = None
+
+    def num_keep(self, num_patches: int) -> int:
+        """``max(1, int(num_tokens * (1 - prob)))`` of :47-48"""
+        return patch_keep_count(num_patches, self.prob)
+
+    def extra_repr(self):
+        return f"prob={self.prob}, exclude_first_token=True"
+
+    def forward(self, *a, **k):  # pragma: no cover
+        raise RuntimeError("parameter container; use NativeCLIP.forward / encode_image")
+
+
+class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: learnable pos, 'tok' pool)
+    def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, quick_gelu=False, patch_dropout=0.0):
+        super().__init__()
+        patch_dropout = 0.0 if patch_dropout is None else patch_dropout
+        if not 0 <= patch_dropout < 1:
+            raise ValueError(f"patch_dropout must satisfy 0 <= prob < 1 (got {patch_dropout!r})")
+        # transformer.py:658: an identity placeholder when the option is off
+        self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0.0 else nn.Identity()
         self.image_size = (image_size, image_size)
         self.patch_size = (patch_size, patch_size)
         self.grid_size = (image_size // patch_size, image_size // patch_size)
@@ -878,10 +923,20 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
     def lock(self, unlocked_groups=0, freeze_bn_stats=False):  # transformer.py:745-753
         _lock_layer_groups(self.layer_groups(), unlocked_groups)
 
-    def forward(self, image, normalize=False, ex=None):
+    def live_tokens(self) -> int:
+        """tokens per image the tower executes as the module stands now: K + 1 in training mode with patch dropout on, else every patch + 1"""
+        G = self.grid_size[0] * self.grid_size[1]
+        pd = self.patch_dropout
+        return (pd.num_keep(G) if self.training and isinstance(pd, PatchDropout) else G) + 1
+
+    def forward(self, image, normalize=False, ex=None, keep=None):
         """``image``: float [B,3,H,W] (already normalised, as the reference's transform produces) or uint8 pixels
         ([B,3,H,W], or [B,H,W,3] as decoders emit them) which are normalised with ``image_mean`` / ``image_std`` in the
-        patch kernel.  ``ex``: the _Exec of this call (NativeCLIP.encode_image passes the model's switches; default: _Exec's own defaults)."""
+        patch kernel.  ``ex``: the _Exec of this call (NativeCLIP.encode_image passes the model's switches; default: _Exec's own defaults).
+        ``keep``: int32 [B, K'] device tensor of patch indices (distinct per image, inside [0, G), any order, any 1 <= K' <= G): the tower runs on the
+        class token and exactly those patches, in training and in eval mode, instead of the random plan of ``patch_dropout`` (fixed or MAE-style
+        masks; parity tests).  Without it, training mode with ``patch_dropout > 0`` draws a uniformly random K-subset per image on the device from a
+        seed taken from torch's global CPU generator (``torch.manual_seed`` governs it; no device synchronisation)."""
         ex = ex if ex is not None else _Exec(self._cache)
         B = image.shape[0]
         norm = None
@@ -893,9 +948,20 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
             hw = tuple(image.shape[2:])
         if hw != tuple(self.image_size):
             raise RuntimeError(f"image size {hw} != {self.image_size}")
-        T = self.grid_size[0] * self.grid_size[1] + 1
+        G = self.grid_size[0] * self.grid_size[1]
+        pd, inv = self.patch_dropout, None
+        if keep is not None:
+            if not (torch.is_tensor(keep) and keep.dtype == torch.int32 and keep.dim() == 2 and keep.shape[0] == B and 1 <= keep.shape[1] <= G):
+                raise ValueError(f"keep must be an int32 [B = {B}, K] tensor of patch indices with 1 <= K <= {G}")
+            keep = keep.contiguous()
+        elif self.training and isinstance(pd, PatchDropout):
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())  # host draw from the global CPU generator: no device work
+            keep, inv = ops.patch_keep_plan(seed, B, G, pd.num_keep(G), image.device)
+            pd.last_keep = keep
+        T = (G if keep is None else keep.shape[1]) + 1
+        drop = () if keep is None else (keep, inv)  # without a plan the call is the one it always was
         x = _VisionEmbedFn.apply(image, self.conv1.weight, self.class_embedding, self.positional_embedding,
-                                 self.ln_pre.weight, self.ln_pre.bias, ex, self.patch_size[0], norm)
+                                 self.ln_pre.weight, self.ln_pre.bias, ex, self.patch_size[0], norm, *drop)
         seq = torch.arange(B, device=x.device, dtype=torch.int32)
         rows = seq * T  # the class token of every image
         return _tower_features(self.transformer, x, ex, B, T, False, None, rows, seq, _pooled_last_block_ok(self), self.ln_post, self.proj, normalize)
@@ -910,9 +976,9 @@ class NativeCLIP(nn.Module):
     # options of the reference's CLIPVisionCfg / CLIPTextCfg / CLIP.__init__ (model.py:27-131, :318-365) that the native path implements,
     # with the only value it implements for the others (the reference dataclass default): anything else must fail loudly instead of
     # training a silently different model (e.g. a *-quickgelu config or a SigLIP-style pooling registered through add_model_config)
-    _VISION_KEYS = {"layers", "width", "head_width", "mlp_ratio", "patch_size", "image_size"}
+    _VISION_KEYS = {"layers", "width", "head_width", "mlp_ratio", "patch_size", "image_size", "patch_dropout"}
     _TEXT_KEYS_OK = {"context_length", "vocab_size", "width", "heads", "layers", "mlp_ratio"}
-    _VISION_DEFAULTS = {"ls_init_value": None, "patch_dropout": 0.0, "attentional_pool": False, "pos_embed_type": "learnable", "no_ln_pre": False,
+    _VISION_DEFAULTS = {"ls_init_value": None, "attentional_pool": False, "pos_embed_type": "learnable", "no_ln_pre": False,
                         "pool_type": "tok", "final_ln_after_pool": False, "output_tokens": False, "act_kwargs": None, "norm_kwargs": None,
                         "block_type": None, "qk_norm": False, "scaled_cosine_attn": False, "scale_heads": False, "scale_attn_inner": False,
                         "scale_attn": False, "scale_fc": False, "timm_model_name": None, "in_chans": 3}
@@ -968,7 +1034,7 @@ class NativeCLIP(nn.Module):
         # OpenAI / LAION-400M checkpoints)
         self.quick_gelu = bool(quick_gelu)
         self.visual = VisionTransformer(v["image_size"], v["patch_size"], v["width"], v["layers"], v["width"] // head_width,
-                                        v.get("mlp_ratio", 4.0), embed_dim, self.quick_gelu)
+                                        v.get("mlp_ratio", 4.0), embed_dim, self.quick_gelu, v.get("patch_dropout", 0.0))
         tw = t["width"]
         self.transformer = Transformer(tw, t["layers"], t["heads"], t.get("mlp_ratio", 4.0), self.quick_gelu)
         self.context_length = t["context_length"]
@@ -1061,9 +1127,11 @@ class NativeCLIP(nn.Module):
         output (4C), ln_1 / ln_2 outputs (2C + 2C), qkv (6C), the attention output (2C), the fp32 middle of the residual stream (4C), the
         8-bit gelu' and the MLP activation (1 + 2 bytes per element of the block's REAL MLP width: 12 C at mlp_ratio 4, 26 C for ViT-e-14) = 20 C +
         3 * mlp_width, + the attention row statistics.  A recomputed block keeps its 4C input only.
-        ``text_rows``: rows of the packed text batch (default: every one of ``context_length`` positions)."""
+        ``text_rows``: rows of the packed text batch (default: every one of ``context_length`` positions).  The image rows are the LIVE ones: in
+        training mode with patch dropout on, the class token and the ``num_keep(G)`` kept patches of the random plan (a ``keep`` passed to a
+        single call, whose K' may differ, is not known here and not counted)."""
         v, t = self.visual, self.transformer
-        rows_v = batch_size * (v.grid_size[0] * v.grid_size[1] + 1)
+        rows_v = batch_size * v.live_tokens()
         rows_t = batch_size * self.context_length if text_rows is None else int(text_rows)
         per = lambda rows, tr, sb: rows * ((12 + 2 * sb) * tr.width + 3 * tr.resblocks[0].mlp.c_fc.out_features + 4 * tr.resblocks[0].n_head + 8)
         # sb = bytes per element of the tower's residual stream: the block output and the middle of the stream are saved in that dtype
@@ -1092,8 +1160,9 @@ class NativeCLIP(nn.Module):
         return _Exec(self.visual._cache if image_tower else self._cache, self.pair_wgrad and not overlap, self.deterministic,
                      bool(self.pooled_single_query), self.image_stream if image_tower else "fp32")
 
-    def encode_image(self, image, normalize: bool = False, _overlap=False):
-        return self.visual(image, normalize, self._exec_options(True, _overlap))
+    def encode_image(self, image, normalize: bool = False, keep=None, _overlap=False):
+        """``keep``: see VisionTransformer.forward (int32 [B, K'] kept patch indices overriding the patch-dropout plan of this call)"""
+        return self.visual(image, normalize, self._exec_options(True, _overlap), keep)
 
     def encode_text(self, text, normalize: bool = False, _pack=None, _overlap=False):
         B, L = text.shape
@@ -1123,7 +1192,8 @@ class NativeCLIP(nn.Module):
         li = _LogitsFn.apply(i, t, self.logit_scale, self.logit_bias)
         return li, li.T
 
-    def forward(self, image: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None):
+    def forward(self, image: Optional[torch.Tensor] = None, text: Optional[torch.Tensor] = None, *, patch_keep: Optional[torch.Tensor] = None):
+        """``patch_keep``: the ``keep`` of ``encode_image`` for this call"""
         # the packed text layout is planned first: its 4-byte read-back then completes while the image tower is being enqueued
         pack = _TextPack(text, self.vocab_size, self.attn_buckets) if (text is not None and self.pack_text) else None
         overlap = self.tower_streams and image is not None and text is not None
@@ -1136,17 +1206,19 @@ class NativeCLIP(nn.Module):
             serial = self.tower_streams == "serial"  # one tower at a time, on the same two streams (see _AfterStream)
             side.wait_stream(cur)
             with torch.cuda.stream(side):
-                image_features = self.encode_image(image, normalize=True, _overlap=True)
+                image_features = self.encode_image(image, normalize=True, keep=patch_keep, _overlap=True)
                 if serial and image_features.requires_grad:
                     image_features = _AfterStream.apply(image_features, cur)
             if serial:
                 cur.wait_stream(side)
             text_features = self.encode_text(text, normalize=True, _pack=pack, _overlap=True)
             image.record_stream(side)
+            if patch_keep is not None:
+                patch_keep.record_stream(side)
             cur.wait_stream(side)
             image_features.record_stream(cur)
         else:
-            image_features = self.encode_image(image, normalize=True) if image is not None else None
+            image_features = self.encode_image(image, normalize=True, keep=patch_keep) if image is not None else None
             text_features = self.encode_text(text, normalize=True, _pack=pack) if text is not None else None
         if self.output_dict:
             out = {"image_features": image_features, "text_features": text_features, "logit_scale": self.logit_scale.exp()}
@@ -1188,7 +1260,8 @@ def convert_to_custom_text_state_dict(state_dict: dict) -> dict:
 
 
 def create_model(model_name: str, pretrained: Optional[str] = None, precision: str = "amp_bf16", device="cuda",
-                 output_dict: Optional[bool] = None, init_logit_scale=None, init_logit_bias=None, force_quick_gelu: bool = False, **model_kwargs):
+                 output_dict: Optional[bool] = None, init_logit_scale=None, init_logit_bias=None, force_quick_gelu: bool = False,
+                 force_patch_dropout: Optional[float] = None, **model_kwargs):
     """Counterpart of ``open_clip.factory.create_model`` (factory.py:264-287) for the native path.
     ``pretrained`` may be a local ``.pt`` state-dict path (no hub access); ``precision`` must be an
     amp_bf16-equivalent mode (the kernels implement exactly that policy)."""
@@ -1215,6 +1288,8 @@ def create_model(model_name: str, pretrained: Optional[str] = None, precision: s
     if init_logit_bias is not None:
         kw["init_logit_bias"] = init_logit_bias
     kw = {k: v for k, v in kw.items() if v is not None}
+    if force_patch_dropout is not None:  # factory.py:460-461: override the config's value (--force-patch-dropout)
+        cfg["vision_cfg"] = dict(cfg["vision_cfg"], patch_dropout=force_patch_dropout)
     if force_quick_gelu:  # factory.py:521-523: override for checkpoints trained with QuickGELU
         extra_model_kwargs["quick_gelu"] = True
     out_dict = output_dict if output_dict is not None else cfg_output_dict

@@ -57,8 +57,10 @@ const char* ocn_last_error(void);
  *                  ocn_scale_rows_bf16, ocn_sub_scaled_rows.
  *   104 (round 6)  new: ocn_set_tile_rescue / ocn_get_tile_rescue (no signature changed).
  *   105            patch dropout of the image tower: new ocn_patch_keep_plan, ocn_patch_keep_inverse, ocn_patchify_keep, ocn_patchify_u8_keep,
- *                  ocn_embed_assemble_keep_fwd, ocn_embed_assemble_keep_bwd (no signature changed). */
-#define OCN_ABI_VERSION 105
+ *                  ocn_embed_assemble_keep_fwd, ocn_embed_assemble_keep_bwd (no signature changed).
+ *   106            BREAKING: one entry point per image-embedding op.  ocn_patchify / ocn_patchify_u8 / ocn_embed_assemble_fwd take a nullable `keep` and K,
+ *                  ocn_embed_assemble_bwd a nullable `inv` and K; the four `_keep` twins of 105 are gone. */
+#define OCN_ABI_VERSION 106
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -187,50 +189,41 @@ int ocn_attn_pooled_fwd(const void* q, const void* kv, void* out, float* lse, co
 int ocn_attn_pooled_bwd(const void* q, const void* kv, const void* out, const void* dout, const float* lse, void* dq, void* dkv,
                         const int32_t* seq_off, const int32_t* rows, int B, int L, int H, int causal, float scale, ocn_stream_t stream);
 
-/* ---- image tower embedding (transformer.py:793-808) -------------------------------------------
- * patchify: image [B,3,H,W] (fp32, or bf16 when image_is_bf16) -> patches bf16 [B*gh*gw, Kpad], column order
- *   (c, i, j) = conv1.weight.reshape(width, 3*P*P) (transformer.py:632-638, :794-796); zero-padded to Kpad.
- * embed_assemble_fwd: emb[b,0,:] = cls + pos[0]; emb[b,1+g,:] = patch_out[b*G+g,:] + pos[1+g]  (:799-801)
- * embed_assemble_bwd: dpatch bf16 [B*G, C] = demb[b,1+g,:]; dpos[T,C] += sum_b demb; dcls[C] += sum_b demb[b,0] */
-int ocn_patchify(const void* image, int image_is_bf16, void* patches, int B, int H, int W, int P, int Kpad,
-                 ocn_stream_t stream);
-/* uint8 input path (8f-4): pixels as decoded ([B,H,W,3] when hwc, else [B,3,H,W]); the kernel applies ToTensor + Normalize
- * ((x/255 - mean[c]) / std[c]; mean3 / std3 = HOST pointers to 3 floats, src/open_clip/constants.py:1-2) while building the
- * same bf16 patch matrix as ocn_patchify. */
-int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, void* patches, int B, int H, int W,
-                    int P, int Kpad, ocn_stream_t stream);
-int ocn_embed_assemble_fwd(const float* patch_out, const float* cls, const float* pos, float* emb, int B, int G, int C,
-                           ocn_stream_t stream);
-int ocn_embed_assemble_bwd(const float* demb, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int C,
-                           int deterministic, ocn_stream_t stream);
-
-/* ---- patch dropout (transformer.py:17-58 PatchDropout; built at :658, applied at :804 behind class token and positions) --------------
+/* ---- patch dropout: which patches survive (transformer.py:17-58 PatchDropout; built at :658, applied at :804 behind class token and positions) ----
  * The reference embeds all G patches and then gathers K = max(1, int(G * (1 - prob))) random ones per image (:47-56).  Which ones survive does
- * not depend on their values: here they are chosen first and only those K are patchified, multiplied and assembled.
+ * not depend on their values: here they are chosen first and only those K are patchified, multiplied and assembled (`keep` / `inv` below).
  * ocn_patch_keep_plan (transformer.py:47-51, the keep count, `randn(batch, num_tokens)` + `topk(num_patches_keep)`): for every image a 32-bit key per patch
  *   from Philox4x32-10 with counter (g, b, 0, 0) and key `seed` -- a function of (seed, b, g) alone -- and the K largest keys kept (ties by index):
  *   a uniformly random K-subset.  keep int32 [B, K]: the kept patch indices of image b ASCENDING; inv int32 [B, G]: position of patch g in
  *   keep[b], or -1.  Nothing comes back to the host.  1 <= K <= G <= 4096; one workgroup per image.
  * ocn_patch_keep_inverse (the index map autograd keeps for the gather of transformer.py:53): inv of a keep the CALLER supplies (any order; the K indices
- *   of an image must be distinct and inside [0, G) -- an index outside is clamped by every kernel that reads keep, so no access leaves a buffer).
- * ocn_patchify_keep / ocn_patchify_u8_keep (transformer.py:794-796 on the kept patches only): ocn_patchify / ocn_patchify_u8 whose output row
- *   b*K + j is patch keep[b, j] of image b: patches bf16 [B*K, Kpad]; keep is honoured in the order given.
- * ocn_embed_assemble_keep_fwd (transformer.py:799-804; :53-56 the gather and the class token in front): emb [B, K+1, C]; emb[b,0] = cls + pos[0];
- *   emb[b,1+j] = patch_out[b*K+j] + pos[1 + keep[b,j]] -- the position is added before the drop, so a kept patch carries its own.
- * ocn_embed_assemble_keep_bwd (autograd of the same: transformer.py:799-804, :53-56): dpatch bf16 [B*K, C] = demb[b,1+j]; dcls += sum_b demb[b,0]; dpos[0] += the same;
- *   dpos[1+g] += sum over the images with inv[b,g] >= 0 of demb[b, 1 + inv[b,g]] -- a gather per (position, channel) like
- *   ocn_embed_assemble_bwd, fp32 atomics per batch chunk or (deterministic) a single writer in batch order.  dpatch is reached through inv alone: a row of keep that inv does
- *   not point back to (a caller's keep with a repeated or clamped index) is not written -- the caller zero-fills dpatch for such a keep. */
+ *   of an image must be distinct and inside [0, G) -- an index outside is clamped by every kernel that reads keep, so no access leaves a buffer). */
 int ocn_patch_keep_plan(int64_t seed, int B, int G, int K, int32_t* keep, int32_t* inv, ocn_stream_t stream);
 int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int K, ocn_stream_t stream);
-int ocn_patchify_keep(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P, int Kpad,
-                      ocn_stream_t stream);
-int ocn_patchify_u8_keep(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches, int B,
-                         int H, int W, int P, int Kpad, ocn_stream_t stream);
-int ocn_embed_assemble_keep_fwd(const float* patch_out, const float* cls, const float* pos, const int32_t* keep, float* emb, int B, int G, int K,
-                                int C, ocn_stream_t stream);
-int ocn_embed_assemble_keep_bwd(const float* demb, const int32_t* inv, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int K, int C,
-                                int deterministic, ocn_stream_t stream);
+
+/* ---- image tower embedding (transformer.py:793-808) -------------------------------------------
+ * All four take the patches of a patch-dropout step as an optional index map, G = gh*gw = (H/P)*(W/P) patches per image of which K are embedded:
+ *   keep int32 [B, K] (1 <= K <= G, honoured in the order given; ocn_patch_keep_plan or the caller's) for the forward functions, its inverse inv
+ *   int32 [B, G] for the backward.  keep == NULL / inv == NULL: every patch in grid order, i.e. keep[b, j] = j and inv[b, g] = g, and then K MUST
+ *   equal G -- anything else is refused before any launch.
+ * ocn_patchify (transformer.py:794-796): image [B,3,H,W] (fp32, or bf16 when image_is_bf16) -> patches bf16 [B*K, Kpad]; row b*K + j is patch
+ *   keep[b, j] of image b, column order (c, i, j) = conv1.weight.reshape(width, 3*P*P) (:632-638); zero-padded to Kpad.  Dropped patches are never read.
+ * ocn_patchify_u8, the uint8 input path (8f-4): pixels as decoded ([B,H,W,3] when hwc, else [B,3,H,W]); the kernel applies ToTensor + Normalize
+ *   ((x/255 - mean[c]) / std[c]; mean3 / std3 = HOST pointers to 3 floats, src/open_clip/constants.py:1-2) while building the same bf16 patch matrix.
+ * ocn_embed_assemble_fwd (:799-804; :53-56 the gather and the class token in front): emb fp32 [B, K+1, C]; emb[b,0] = cls + pos[0];
+ *   emb[b,1+j] = patch_out[b*K+j] + pos[1 + keep[b,j]] -- the position is added before the drop, so a kept patch carries its own.
+ * ocn_embed_assemble_bwd (autograd of the same): dpatch bf16 [B*K, C] = demb[b,1+j]; dcls[C] += sum_b demb[b,0]; dpos[0] += the same;
+ *   dpos[1+g] += sum over the images with inv[b,g] >= 0 of demb[b, 1 + inv[b,g]] -- a gather per (position, channel), fp32 atomics per batch chunk
+ *   or (deterministic) a single writer in batch order.  dpatch is reached through inv alone: a row of keep that inv does not point back to (a
+ *   caller's keep with a repeated or clamped index) is not written -- the caller zero-fills dpatch for such a keep. */
+int ocn_patchify(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P, int Kpad,
+                 ocn_stream_t stream);
+int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches, int B,
+                    int H, int W, int P, int Kpad, ocn_stream_t stream);
+int ocn_embed_assemble_fwd(const float* patch_out, const float* cls, const float* pos, const int32_t* keep, float* emb, int B, int G, int K,
+                           int C, ocn_stream_t stream);
+int ocn_embed_assemble_bwd(const float* demb, const int32_t* inv, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int K, int C,
+                           int deterministic, ocn_stream_t stream);
 
 /* ---- text tower embedding (model.py:399-401) ---------------------------------------------------
  * fwd: x[b,l,:] = table[text[b,l],:] + pos[l,:];  bwd: dtable[text[b,l],:] += dx[b,l,:] (fp32 atomics),

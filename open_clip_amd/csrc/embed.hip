@@ -1,4 +1,5 @@
-// HBM-bound embedding / pooling / normalisation kernels around the two transformer stacks.
+// HBM-bound embedding / pooling / normalisation kernels around the two transformer stacks.  The image embedding (patchify, class token +
+// positions) takes an optional `keep` / `inv` from patch_dropout.hip, which only decides WHICH patches survive; everything done with them is here.
 #include "ocn_common.h"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
@@ -10,8 +11,7 @@ namespace {
 // training step drops are never read.  An index outside [0, G) is clamped (as the token kernels clamp ids): no read can leave the image.
 OCN_DEV int kept_patch(const int32_t* __restrict__ keep, long row, int R, int G) {
     if (!keep) return (int)(row % R);
-    const int g = keep[row];
-    return g < 0 ? 0 : (g >= G ? G - 1 : g);
+    return ocn_clamp_index(keep[row], G);
 }
 
 template <typename T, int VEC>
@@ -107,43 +107,60 @@ __global__ __launch_bounds__(256) void patchify_u8_hwc_kernel(const unsigned cha
     }
 }
 
-// ---- class token + positional embedding (transformer.py:799-801) --------------------------------
-__global__ void embed_assemble_fwd_kernel(const float* __restrict__ po, const float* __restrict__ cls,
-                                          const float* __restrict__ pos, float* __restrict__ emb, int B, int G, int C) {
-    const int T = G + 1, c4n = C / 4;
+// ---- class token + positional embedding (transformer.py:799-804) --------------------------------
+// emb[b, 0] = cls + pos[0]; emb[b, 1 + j] = po[b*K + j] + pos[1 + keep[b, j]]: the position is added BEFORE the drop (gather :53-56), so a kept patch
+// carries its own.  KEEP = false (keep = NULL): every patch in grid order (K == G).
+template <bool KEEP>
+__global__ void embed_assemble_fwd_kernel(const float* __restrict__ po, const float* __restrict__ cls, const float* __restrict__ pos,
+                                          const int32_t* __restrict__ keep, float* __restrict__ emb, int B, int G, int K, int C) {
+    const int T = K + 1, c4n = C / 4;
     const long total = (long)B * T * c4n;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int c = (int)(idx % c4n) * 4;
         const long bt = idx / c4n;
         const int t = (int)(bt % T);
         const long b = bt / T;
-        const f32x4 p = *(const f32x4*)(pos + (size_t)t * C + c);
-        const f32x4 v = (t == 0) ? *(const f32x4*)(cls + c) : *(const f32x4*)(po + ((size_t)b * G + t - 1) * C + c);
-        *(f32x4*)(emb + (size_t)bt * C + c) = v + p;
+        const int p = t == 0 ? 0 : 1 + (KEEP ? ocn_clamp_index(keep[b * K + t - 1], G) : t - 1);
+        const f32x4 pv = *(const f32x4*)(pos + (size_t)p * C + c);
+        const f32x4 v = (t == 0) ? *(const f32x4*)(cls + c) : *(const f32x4*)(po + ((size_t)b * K + t - 1) * C + c);
+        *(f32x4*)(emb + (size_t)bt * C + c) = v + pv;
     }
 }
 
-// grid.x covers (t, c4); grid.y = batch chunks.  dpos/dcls by fp32 atomics (one per chunk per element).
-__global__ void embed_assemble_bwd_kernel(const float* __restrict__ demb, bf16* __restrict__ dpatch,
-                                          float* __restrict__ dpos, float* __restrict__ dcls, int B, int G, int C, int bchunk) {
-    const int T = G + 1, c4n = C / 4;
+// grid.x covers (position p of the FULL grid, c4), p = 0 the class token, p = 1 + g patch g; grid.y = batch chunks.  A gather through inv: image b
+// contributes demb[b, 1 + inv[b, g]] to position 1 + g when it kept that patch -- and that (b, g) is the one place the row is met, so its bf16
+// copy dpatch[b*K + inv[b, g]] is written there too (KEEP = false, inv = NULL: every patch kept at its own place, K == G).  dpos / dcls: one fp32 atomic per
+// chunk per element, or (bchunk = B) a single writer in batch order.  A position no image of the chunk kept adds nothing.
+template <bool KEEP>
+__global__ void embed_assemble_bwd_kernel(const float* __restrict__ demb, const int32_t* __restrict__ inv, bf16* __restrict__ dpatch,
+                                          float* __restrict__ dpos, float* __restrict__ dcls, int B, int G, int K, int C, int bchunk) {
+    const int T = K + 1, c4n = C / 4;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T * c4n) return;
-    const int t = idx / c4n, c = (idx % c4n) * 4;
+    if (idx >= (G + 1) * c4n) return;
+    const int p = idx / c4n, c = (idx % c4n) * 4;
     const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    bool any = false;
     for (int b = b0; b < b1; ++b) {
+        int t = 0;
+        if (p > 0) {
+            const int j = KEEP ? inv[(size_t)b * G + p - 1] : p - 1;
+            if (j < 0 || j >= K) continue;
+            t = 1 + j;
+        }
         const f32x4 v = *(const f32x4*)(demb + ((size_t)b * T + t) * C + c);
         acc = acc + v;
+        any = true;
         if (t > 0) {
             bf16x4 o4 = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-            *(bf16x4*)(dpatch + ((size_t)b * G + t - 1) * C + c) = o4;
+            *(bf16x4*)(dpatch + ((size_t)b * K + t - 1) * C + c) = o4;
         }
     }
+    if (!any) return;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        unsafeAtomicAdd(dpos + (size_t)t * C + c + e, acc[e]);
-        if (t == 0) unsafeAtomicAdd(dcls + c + e, acc[e]);
+        unsafeAtomicAdd(dpos + (size_t)p * C + c + e, acc[e]);
+        if (p == 0) unsafeAtomicAdd(dcls + c + e, acc[e]);
     }
 }
 
@@ -156,8 +173,7 @@ __global__ void token_embed_fwd_kernel(const int64_t* __restrict__ text, const f
         const int c = (int)(idx % c4n) * 4;
         const long bl = idx / c4n;
         const int l = (int)(bl % L);
-        long tok = text[bl];
-        tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+        const long tok = ocn_clamp_index(text[bl], (long)vocab);
         *(f32x4*)(x + (size_t)bl * C + c) = *(const f32x4*)(table + (size_t)tok * C + c) + *(const f32x4*)(pos + (size_t)l * C + c);
     }
 }
@@ -178,8 +194,7 @@ __global__ void token_embed_bwd_kernel(const int64_t* __restrict__ text, const f
     for (int b = b0; b < b1; ++b) {
         const float v = dx[((size_t)b * L + l) * C + c];
         acc += v;
-        long tok = text[(size_t)b * L + l];
-        tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+        const long tok = ocn_clamp_index(text[(size_t)b * L + l], (long)vocab);
         if (tok != run_tok) {
             if (run_tok >= 0) unsafeAtomicAdd(dtable + (size_t)run_tok * C + c, run);
             run_tok = tok;
@@ -214,10 +229,7 @@ __global__ __launch_bounds__(128) void token_embed_bwd_sorted_kernel(const int64
     const long i0 = (long)blockIdx.x * CH, i1 = min(n, i0 + CH);
     // a run is identified by the CLAMPED id (ids outside the vocabulary share row 0 / vocab - 1), so whether a run continues into the
     // neighbouring chunk is decided on clamped ids too: two chunks must never both take one row for a complete run and plain-store it
-    auto clamped = [&](long i) -> long {
-        const long t = keys[i];
-        return t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
-    };
+    auto clamped = [&](long i) -> long { return ocn_clamp_index(keys[i], (long)vocab); };
     if (det) {
         // reproducible form (NativeCLIP(deterministic=True)): a run of equal ids is summed by ONE workgroup -- the one whose chunk holds the run's
         // first entry walks it to its end, wherever that is, in sorted (stable) order, and plain-stores the row; a chunk that begins inside a run
@@ -336,8 +348,7 @@ __global__ void token_embed_fwd_rows_kernel(const int64_t* __restrict__ tokens, 
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int c = (int)(idx % c4n) * 4;
         const long r = idx / c4n;
-        long tok = tokens[r];
-        tok = tok < 0 ? 0 : (tok >= vocab ? vocab - 1 : tok);
+        const long tok = ocn_clamp_index(tokens[r], (long)vocab);
         *(f32x4*)(x + (size_t)r * C + c) = *(const f32x4*)(table + (size_t)tok * C + c) + *(const f32x4*)(pos + (size_t)posidx[r] * C + c);
     }
 }
@@ -486,97 +497,80 @@ __global__ void l2norm_bwd_kernel(const float* __restrict__ dy, const float* __r
     for (int c = lane; c < E; c += 64) dx[(size_t)row * E + c] = (dy[(size_t)row * E + c] - y[(size_t)row * E + c] * s) * inv;
 }
 
-int grid_for(long items, int block) {
-    long g = (items + block - 1) / block;
-    return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
-}
-
 }  // namespace
 
-static int patchify_impl(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P, int Kpad,
-                         ocn_stream_t stream) {
+// keep == NULL: every patch in grid order, and the caller's K must say so (K == G) -- a K that were ignored is how a B*K buffer meets a B*G launch
+#define OCN_CHECK_KEEP(name, keep, K, G)                                                                                          \
+    OCN_CHECK_ARG((keep) ? ((K) >= 1 && (K) <= (G)) : (K) == (G), name ": K=%d with G=%d (1 <= K <= G with keep / inv, K == G without)", K, G)
+
+extern "C" int ocn_patchify(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P, int Kpad,
+                            ocn_stream_t stream) {
     OCN_CHECK_ARG(image && patches, "ocn_patchify: null operand");
     OCN_CHECK_ARG(B > 0 && P > 0 && H % P == 0 && W % P == 0 && P % 2 == 0, "ocn_patchify: bad geometry H=%d W=%d P=%d", H, W, P);
     OCN_CHECK_ARG(Kpad >= 3 * P * P && Kpad % 4 == 0, "ocn_patchify: Kpad=%d too small / not a multiple of 4", Kpad);
+    OCN_CHECK_KEEP("ocn_patchify", keep, K, (H / P) * (W / P));
     hipStream_t st = (hipStream_t)stream;
-    const long rows = (long)B * (keep ? K : (H / P) * (W / P));
+    const long rows = (long)B * K;
     if (P % 4 == 0) {
         const long total = rows * (Kpad / 4);
-        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
-        else hipLaunchKernelGGL((patchify_kernel<float, 4>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 4>), dim3(ocn_grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        else hipLaunchKernelGGL((patchify_kernel<float, 4>), dim3(ocn_grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
     } else {
         const long total = rows * (Kpad / 2);
-        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
-        else hipLaunchKernelGGL((patchify_kernel<float, 2>), dim3(grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        if (image_is_bf16) hipLaunchKernelGGL((patchify_kernel<bf16, 2>), dim3(ocn_grid_for(total, 256)), dim3(256), 0, st, (const bf16*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
+        else hipLaunchKernelGGL((patchify_kernel<float, 2>), dim3(ocn_grid_for(total, 256)), dim3(256), 0, st, (const float*)image, (bf16*)patches, B, H, W, P, Kpad, total, keep, K);
     }
     OCN_CHECK_LAUNCH("ocn_patchify");
     return OCN_OK;
 }
 
-extern "C" int ocn_patchify(const void* image, int image_is_bf16, void* patches, int B, int H, int W, int P, int Kpad,
-                            ocn_stream_t stream) {
-    return patchify_impl(image, image_is_bf16, nullptr, 0, patches, B, H, W, P, Kpad, stream);
-}
-
-extern "C" int ocn_patchify_keep(const void* image, int image_is_bf16, const int32_t* keep, int K, void* patches, int B, int H, int W, int P,
-                                 int Kpad, ocn_stream_t stream) {
-    OCN_CHECK_ARG(keep && K > 0, "ocn_patchify_keep: keep is null or K = %d", K);
-    return patchify_impl(image, image_is_bf16, keep, K, patches, B, H, W, P, Kpad, stream);
-}
-
-static int patchify_u8_impl(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches, int B,
-                            int H, int W, int P, int Kpad, ocn_stream_t stream) {
+extern "C" int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches, int B,
+                               int H, int W, int P, int Kpad, ocn_stream_t stream) {
     OCN_CHECK_ARG(image_u8 && patches && mean3 && std3, "ocn_patchify_u8: null operand");
     OCN_CHECK_ARG(B > 0 && P > 0 && H % P == 0 && W % P == 0 && P % 2 == 0, "ocn_patchify_u8: bad geometry H=%d W=%d P=%d", H, W, P);
     OCN_CHECK_ARG(Kpad >= 3 * P * P && Kpad % 4 == 0, "ocn_patchify_u8: Kpad=%d too small / not a multiple of 4", Kpad);
+    OCN_CHECK_KEEP("ocn_patchify_u8", keep, K, (H / P) * (W / P));
     NormC nc;
     for (int c = 0; c < 3; ++c) {  // mean3 / std3 are HOST pointers (three floats each)
         OCN_CHECK_ARG(std3[c] > 0.f, "ocn_patchify_u8: std must be positive");
         nc.scale[c] = 1.0f / (255.0f * std3[c]);
         nc.shift[c] = -mean3[c] / std3[c];
     }
+    const long npatch = (long)B * K;
     if (hwc && P % 16 == 0 && Kpad % 8 == 0 && ((uintptr_t)image_u8 & 15) == 0 && ((uintptr_t)patches & 15) == 0) {
-        const long npatch = (long)B * (keep ? K : (H / P) * (W / P));
         hipLaunchKernelGGL(patchify_u8_hwc_kernel, dim3((unsigned)(npatch < 16384 ? npatch : 16384)), dim3(256), 3 * P * P, (hipStream_t)stream,
                            (const unsigned char*)image_u8, (bf16*)patches, H, W, P, Kpad, npatch, nc, keep, K);
         OCN_CHECK_LAUNCH("ocn_patchify_u8");
         return OCN_OK;
     }
-    const long total = (long)B * (keep ? K : (H / P) * (W / P)) * (Kpad / 2);
-    hipLaunchKernelGGL(patchify_u8_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image_u8,
+    const long total = npatch * (Kpad / 2);
+    hipLaunchKernelGGL(patchify_u8_kernel, dim3(ocn_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image_u8,
                        (bf16*)patches, B, H, W, P, Kpad, total, hwc, nc, keep, K);
     OCN_CHECK_LAUNCH("ocn_patchify_u8");
     return OCN_OK;
 }
 
-extern "C" int ocn_patchify_u8(const void* image_u8, int hwc, const float* mean3, const float* std3, void* patches, int B, int H, int W,
-                               int P, int Kpad, ocn_stream_t stream) {
-    return patchify_u8_impl(image_u8, hwc, mean3, std3, nullptr, 0, patches, B, H, W, P, Kpad, stream);
-}
-
-extern "C" int ocn_patchify_u8_keep(const void* image_u8, int hwc, const float* mean3, const float* std3, const int32_t* keep, int K, void* patches,
-                                    int B, int H, int W, int P, int Kpad, ocn_stream_t stream) {
-    OCN_CHECK_ARG(keep && K > 0, "ocn_patchify_u8_keep: keep is null or K = %d", K);
-    return patchify_u8_impl(image_u8, hwc, mean3, std3, keep, K, patches, B, H, W, P, Kpad, stream);
-}
-
-extern "C" int ocn_embed_assemble_fwd(const float* patch_out, const float* cls, const float* pos, float* emb, int B, int G,
-                                      int C, ocn_stream_t stream) {
+extern "C" int ocn_embed_assemble_fwd(const float* patch_out, const float* cls, const float* pos, const int32_t* keep, float* emb, int B, int G,
+                                      int K, int C, ocn_stream_t stream) {
     OCN_CHECK_ARG(patch_out && cls && pos && emb, "ocn_embed_assemble_fwd: null operand");
-    OCN_CHECK_ARG(B > 0 && G > 0 && C % 4 == 0, "ocn_embed_assemble_fwd: bad shape");
-    const long total = (long)B * (G + 1) * (C / 4);
-    hipLaunchKernelGGL(embed_assemble_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, patch_out, cls, pos, emb, B, G, C);
+    OCN_CHECK_ARG(B > 0 && G > 0 && C > 0 && C % 4 == 0, "ocn_embed_assemble_fwd: bad shape");
+    OCN_CHECK_KEEP("ocn_embed_assemble_fwd", keep, K, G);
+    const long total = (long)B * (K + 1) * (C / 4);
+    const auto kernel = keep ? embed_assemble_fwd_kernel<true> : embed_assemble_fwd_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(ocn_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, patch_out, cls, pos, keep, emb, B, G, K, C);
     OCN_CHECK_LAUNCH("ocn_embed_assemble_fwd");
     return OCN_OK;
 }
 
-extern "C" int ocn_embed_assemble_bwd(const float* demb, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int C, int deterministic,
-                                      ocn_stream_t stream) {
+extern "C" int ocn_embed_assemble_bwd(const float* demb, const int32_t* inv, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int K, int C,
+                                      int deterministic, ocn_stream_t stream) {
     OCN_CHECK_ARG(demb && dpatch_bf16 && dpos && dcls, "ocn_embed_assemble_bwd: null operand");
-    OCN_CHECK_ARG(B > 0 && G > 0 && C % 4 == 0, "ocn_embed_assemble_bwd: bad shape");
-    const int bchunk = deterministic ? B : 32;  // deterministic: ONE batch chunk -- every element of dpos / dcls has a single writer summing in batch order
+    OCN_CHECK_ARG(B > 0 && G > 0 && C > 0 && C % 4 == 0, "ocn_embed_assemble_bwd: bad shape");
+    OCN_CHECK_KEEP("ocn_embed_assemble_bwd", inv, K, G);
+    const int bchunk = deterministic ? B : 32;  // deterministic: ONE batch chunk -- a single writer per element of dpos / dcls, summing in batch order
     dim3 grid(ocn_cdiv((long)(G + 1) * (C / 4), 256), ocn_cdiv(B, bchunk));
-    hipLaunchKernelGGL(embed_assemble_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, demb, (bf16*)dpatch_bf16, dpos, dcls, B, G, C, bchunk);
+    const auto kernel = inv ? embed_assemble_bwd_kernel<true> : embed_assemble_bwd_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, demb, inv, (bf16*)dpatch_bf16, dpos, dcls, B, G, K, C, bchunk);
     OCN_CHECK_LAUNCH("ocn_embed_assemble_bwd");
     return OCN_OK;
 }
@@ -586,7 +580,7 @@ extern "C" int ocn_token_embed_fwd(const int64_t* text, const float* table, cons
     OCN_CHECK_ARG(text && table && pos && x, "ocn_token_embed_fwd: null operand");
     OCN_CHECK_ARG(B > 0 && L > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_fwd: bad shape");
     const long total = (long)B * L * (C / 4);
-    hipLaunchKernelGGL(token_embed_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, text, table, pos, x, B, L, C, vocab);
+    hipLaunchKernelGGL(token_embed_fwd_kernel, dim3(ocn_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, text, table, pos, x, B, L, C, vocab);
     OCN_CHECK_LAUNCH("ocn_token_embed_fwd");
     return OCN_OK;
 }
@@ -692,7 +686,7 @@ extern "C" int ocn_seq_pack_plan(const int64_t* text, int32_t* eot, int32_t* seq
 extern "C" int ocn_seq_pack_rows(const int64_t* text, const int32_t* seq_off, int64_t* tokens, int32_t* posidx, int B, int L,
                                  ocn_stream_t stream) {
     OCN_CHECK_ARG(text && seq_off && tokens && posidx && B > 0 && L > 0, "ocn_seq_pack_rows: bad arguments");
-    hipLaunchKernelGGL(seq_pack_rows_kernel, dim3(grid_for((long)B * L, 256)), dim3(256), 0, (hipStream_t)stream, text, seq_off, tokens, posidx, B, L);
+    hipLaunchKernelGGL(seq_pack_rows_kernel, dim3(ocn_grid_for((long)B * L, 256)), dim3(256), 0, (hipStream_t)stream, text, seq_off, tokens, posidx, B, L);
     OCN_CHECK_LAUNCH("ocn_seq_pack_rows");
     return OCN_OK;
 }
@@ -701,7 +695,7 @@ extern "C" int ocn_token_embed_fwd_rows(const int64_t* tokens, const int32_t* po
                                         int C, int vocab, ocn_stream_t stream) {
     OCN_CHECK_ARG(tokens && posidx && table && pos && x, "ocn_token_embed_fwd_rows: null operand");
     OCN_CHECK_ARG(M > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_fwd_rows: bad shape");
-    hipLaunchKernelGGL(token_embed_fwd_rows_kernel, dim3(grid_for(M * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, tokens, posidx, table, pos, x, M, C, vocab);
+    hipLaunchKernelGGL(token_embed_fwd_rows_kernel, dim3(ocn_grid_for(M * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, tokens, posidx, table, pos, x, M, C, vocab);
     OCN_CHECK_LAUNCH("ocn_token_embed_fwd_rows");
     return OCN_OK;
 }
@@ -735,8 +729,8 @@ extern "C" int ocn_argmax_rows(const int64_t* text, int32_t* idx, int B, int L, 
 
 extern "C" int ocn_gather_rows(const void* x, int x_is_bf16, const int32_t* idx, float* out, int B, int L, int C, ocn_stream_t stream) {
     OCN_CHECK_ARG(x && out && B > 0 && L >= 0 && (L > 0 || idx) && C % 4 == 0, "ocn_gather_rows: bad arguments");
-    if (x_is_bf16) hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, idx, out, B, L, C);
-    else hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, idx, out, B, L, C);
+    if (x_is_bf16) hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(ocn_grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, idx, out, B, L, C);
+    else hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(ocn_grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, x, idx, out, B, L, C);
     OCN_CHECK_LAUNCH("ocn_gather_rows");
     return OCN_OK;
 }
@@ -755,7 +749,7 @@ __global__ void gather_rows_bf16_kernel(const bf16* __restrict__ x, const int32_
 
 extern "C" int ocn_gather_rows_bf16(const void* x, const int32_t* idx, void* out, int B, int L, int C, ocn_stream_t stream) {
     OCN_CHECK_ARG(x && out && B > 0 && L >= 0 && (L > 0 || idx) && C % 8 == 0, "ocn_gather_rows_bf16: bad arguments");
-    hipLaunchKernelGGL(gather_rows_bf16_kernel, dim3(grid_for((long)B * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, idx,
+    hipLaunchKernelGGL(gather_rows_bf16_kernel, dim3(ocn_grid_for((long)B * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, idx,
                        (bf16*)out, B, L, C);
     OCN_CHECK_LAUNCH("ocn_gather_rows_bf16");
     return OCN_OK;
@@ -764,14 +758,14 @@ extern "C" int ocn_gather_rows_bf16(const void* x, const int32_t* idx, void* out
 extern "C" int ocn_scatter_rows(const float* d, const int32_t* idx, float* dx, void* dx_bf16, int B, int L, int C,
                                 ocn_stream_t stream) {
     OCN_CHECK_ARG(d && (dx || dx_bf16) && B > 0 && L >= 0 && (L > 0 || idx) && C % 4 == 0, "ocn_scatter_rows: bad arguments");
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, d, idx, dx, (bf16*)dx_bf16, B, L, C);
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(ocn_grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, d, idx, dx, (bf16*)dx_bf16, B, L, C);
     OCN_CHECK_LAUNCH("ocn_scatter_rows");
     return OCN_OK;
 }
 
 extern "C" int ocn_scatter_add_rows(const float* d, const int32_t* idx, float* dx, void* dx_bf16, int B, int L, int C, ocn_stream_t stream) {
     OCN_CHECK_ARG(d && (dx || dx_bf16) && B > 0 && L >= 0 && (L > 0 || idx) && C % 4 == 0, "ocn_scatter_add_rows: bad arguments");
-    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, d, idx, dx, (bf16*)dx_bf16, B, L, C);
+    hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(ocn_grid_for((long)B * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, d, idx, dx, (bf16*)dx_bf16, B, L, C);
     OCN_CHECK_LAUNCH("ocn_scatter_add_rows");
     return OCN_OK;
 }

@@ -45,6 +45,10 @@ OCN_DEV bf16 f2bf(float v) { return (bf16)v; }  // round-to-nearest-even (v_cvt_
 // discarded lane -- exp2f() adds a denormal-range rescue (5 more VALU operations per element) that nothing here needs
 OCN_DEV float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
+// an index (token id, patch index) forced into [0, n): a bad one can never read or write outside its table
+template <typename I>
+OCN_DEV I ocn_clamp_index(I v, I n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
 OCN_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -186,3 +190,8 @@ OCN_DEV int xcd_remap(int bid, int nwg) {
 }
 
 static inline int ocn_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// workgroups of a grid-stride launch over `items`: at least 1, at most 8192
+static inline int ocn_grid_for(long items, int block) {
+    long g = (items + block - 1) / block;
+    return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
+}

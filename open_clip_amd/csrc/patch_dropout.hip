@@ -1,9 +1,8 @@
 // Patch dropout of the image tower (reference transformer.py:17-58 `PatchDropout`, applied at :804 after the class token and the positional
 // embedding): which patches survive does not depend on their values, so the native path chooses them FIRST (patch_keep_plan_kernel) and
-// patchifies (embed.hip, `keep` forms), multiplies and assembles only the K kept patches of every image.  All kernels here are HBM-bound gathers.
+// patchifies, multiplies and assembles only the K kept patches of every image.  This file only decides WHICH patches survive (the plan and its
+// inverse); everything that is done with `keep` / `inv` is in embed.hip.
 #include "ocn_common.h"
-
-#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 namespace {
 
@@ -76,70 +75,8 @@ __global__ __launch_bounds__(256) void patch_keep_inverse_kernel(const int32_t* 
     __syncthreads();
     for (int j = threadIdx.x; j < K; j += 256) {
         const int g = keep[(size_t)b * K + j];
-        inv[(size_t)b * G + (g < 0 ? 0 : (g >= G ? G - 1 : g))] = j;
+        inv[(size_t)b * G + ocn_clamp_index(g, G)] = j;
     }
-}
-
-// emb[b, 0] = cls + pos[0]; emb[b, 1 + j] = po[b*K + j] + pos[1 + keep[b, j]]  (transformer.py:799-804, gather :53-56: the position is added BEFORE the drop)
-__global__ void embed_assemble_keep_fwd_kernel(const float* __restrict__ po, const float* __restrict__ cls, const float* __restrict__ pos,
-                                               const int32_t* __restrict__ keep, float* __restrict__ emb, int B, int G, int K, int C) {
-    const int T = K + 1, c4n = C / 4;
-    const long total = (long)B * T * c4n;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long bt = idx / c4n;
-        const int t = (int)(bt % T);
-        const long b = bt / T;
-        int p = 0;
-        if (t > 0) {
-            const int g = keep[b * K + t - 1];
-            p = 1 + (g < 0 ? 0 : (g >= G ? G - 1 : g));
-        }
-        const f32x4 pv = *(const f32x4*)(pos + (size_t)p * C + c);
-        const f32x4 v = (t == 0) ? *(const f32x4*)(cls + c) : *(const f32x4*)(po + ((size_t)b * K + t - 1) * C + c);
-        *(f32x4*)(emb + (size_t)bt * C + c) = v + pv;
-    }
-}
-
-// grid.x covers (position p of the FULL grid, c4), p = 0 the class token, p = 1 + g patch g; grid.y = batch chunks.  A gather through inv: image b
-// contributes demb[b, 1 + inv[b, g]] to position 1 + g when it kept that patch -- and that (b, g) is the one place the row is met, so its bf16
-// copy dpatch[b*K + inv[b, g]] is written there too.  dpos / dcls: one fp32 atomic per chunk per element, or (bchunk = B) a single writer in
-// batch order.  A position no image of the chunk kept adds nothing.
-__global__ void embed_assemble_keep_bwd_kernel(const float* __restrict__ demb, const int32_t* __restrict__ inv, bf16* __restrict__ dpatch,
-                                               float* __restrict__ dpos, float* __restrict__ dcls, int B, int G, int K, int C, int bchunk) {
-    const int T = K + 1, c4n = C / 4;
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (G + 1) * c4n) return;
-    const int p = idx / c4n, c = (idx % c4n) * 4;
-    const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    bool any = false;
-    for (int b = b0; b < b1; ++b) {
-        int t = 0;
-        if (p > 0) {
-            const int j = inv[(size_t)b * G + p - 1];
-            if (j < 0 || j >= K) continue;
-            t = 1 + j;
-        }
-        const f32x4 v = *(const f32x4*)(demb + ((size_t)b * T + t) * C + c);
-        acc = acc + v;
-        any = true;
-        if (t > 0) {
-            bf16x4 o4 = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-            *(bf16x4*)(dpatch + ((size_t)b * K + t - 1) * C + c) = o4;
-        }
-    }
-    if (!any) return;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        unsafeAtomicAdd(dpos + (size_t)p * C + c + e, acc[e]);
-        if (p == 0) unsafeAtomicAdd(dcls + c + e, acc[e]);
-    }
-}
-
-int grid_for(long items, int block) {
-    long g = (items + block - 1) / block;
-    return (int)(g < 8192 ? (g > 0 ? g : 1) : 8192);
 }
 
 }  // namespace
@@ -158,28 +95,5 @@ extern "C" int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, 
     OCN_CHECK_ARG(B > 0 && G > 0 && K > 0 && K <= G, "ocn_patch_keep_inverse: bad shape B=%d G=%d K=%d (1 <= K <= G)", B, G, K);
     hipLaunchKernelGGL(patch_keep_inverse_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, keep, inv, G, K);
     OCN_CHECK_LAUNCH("ocn_patch_keep_inverse");
-    return OCN_OK;
-}
-
-extern "C" int ocn_embed_assemble_keep_fwd(const float* patch_out, const float* cls, const float* pos, const int32_t* keep, float* emb, int B, int G,
-                                           int K, int C, ocn_stream_t stream) {
-    OCN_CHECK_ARG(patch_out && cls && pos && keep && emb, "ocn_embed_assemble_keep_fwd: null operand");
-    OCN_CHECK_ARG(B > 0 && G > 0 && K > 0 && K <= G && C > 0 && C % 4 == 0, "ocn_embed_assemble_keep_fwd: bad shape");
-    const long total = (long)B * (K + 1) * (C / 4);
-    hipLaunchKernelGGL(embed_assemble_keep_fwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, patch_out, cls, pos, keep, emb, B,
-                       G, K, C);
-    OCN_CHECK_LAUNCH("ocn_embed_assemble_keep_fwd");
-    return OCN_OK;
-}
-
-extern "C" int ocn_embed_assemble_keep_bwd(const float* demb, const int32_t* inv, void* dpatch_bf16, float* dpos, float* dcls, int B, int G, int K,
-                                           int C, int deterministic, ocn_stream_t stream) {
-    OCN_CHECK_ARG(demb && inv && dpatch_bf16 && dpos && dcls, "ocn_embed_assemble_keep_bwd: null operand");
-    OCN_CHECK_ARG(B > 0 && G > 0 && K > 0 && K <= G && C > 0 && C % 4 == 0, "ocn_embed_assemble_keep_bwd: bad shape");
-    const int bchunk = deterministic ? B : 32;  // deterministic: ONE batch chunk -- a single writer per element of dpos / dcls, summing in batch order
-    dim3 grid(ocn_cdiv((long)(G + 1) * (C / 4), 256), ocn_cdiv(B, bchunk));
-    hipLaunchKernelGGL(embed_assemble_keep_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, demb, inv, (bf16*)dpatch_bf16, dpos, dcls, B, G, K, C,
-                       bchunk);
-    OCN_CHECK_LAUNCH("ocn_embed_assemble_keep_bwd");
     return OCN_OK;
 }

@@ -486,18 +486,15 @@ class _VisionEmbedFn(torch.autograd.Function):
             w16 = torch.zeros(width, Kpad, dtype=BF16, device=image.device)
             w16[:, :KP].copy_(cache.get(conv_w, "n"))
         po = ops.gemm_nt(ops.EPI_F32, patches, w16, ops.empty((B * K, width), F32, patches))
-        if keep is None:
-            emb = ops.embed_assemble_fwd(po, cls, pos, B, G, width)
-        else:
-            emb = ops.embed_assemble_keep_fwd(po, cls, pos, keep, B, G, width)
-            ctx.own_plan = inv is not None  # the plan kernel's inv reaches every row of keep; a caller's keep may not be a clean subset
-            if inv is None and any(ctx.needs_input_grad):
-                inv = ops.patch_keep_inverse(keep, G)
+        emb = ops.embed_assemble_fwd(po, cls, pos, B, G, width, keep)
+        ctx.own_plan = keep is None or inv is not None  # the plan kernel's inv (or none at all) reaches every row; a caller's keep may not be a clean subset
+        if keep is not None and inv is None and any(ctx.needs_input_grad):
+            inv = ops.patch_keep_inverse(keep, G)
         bf = ex.stream != "fp32"  # bf16 residual stream: ln_pre hands its result on in bf16 (layers.py:23-26 under autocast); emb itself stays fp32 here
         x16, x0, mean, rstd = ops.layernorm_fwd(emb, lnw, lnb, want_bf16=bf, want_f32=not bf)
         x0 = x16 if bf else x0
         ctx.save_for_backward(patches, emb, mean, rstd, lnw, conv_w, cls, pos)
-        ctx.meta = (B, G, width, KP, Kpad)
+        ctx.meta = (B, G, K, width, KP, Kpad)
         ctx.keep, ctx.inv = keep, inv
         ctx.det = ex.deterministic
         return x0
@@ -505,17 +502,14 @@ class _VisionEmbedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx0):
         patches, emb, mean, rstd, lnw, conv_w, cls, pos = ctx.saved_tensors
-        B, G, width, KP, Kpad = ctx.meta
+        B, G, K, width, KP, Kpad = ctx.meta
         dev = emb.device
         dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
         dy0 = (_take_f32(dx0) if dx0.dtype == BF16 else None)  # bf16 stream: the first block's fp32 companion when there is one
         dy0 = dx0.contiguous() if dy0 is None else dy0
         demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.det)
         dpos, dcls = torch.zeros_like(pos), torch.zeros_like(cls)
-        if ctx.keep is None:
-            dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det)
-        else:
-            dpatch = ops.embed_assemble_keep_bwd(demb, ctx.inv, dpos, dcls, B, G, ctx.keep.shape[1], width, ctx.det, zero_dpatch=not ctx.own_plan)
+        dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det, inv=ctx.inv, K=K, zero_dpatch=not ctx.own_plan)
         dw = torch.zeros(width, Kpad, dtype=F32, device=dev)
         ops.gemm_tn_accum(dpatch, patches, dw, None, 1.0, ctx.det)
         dconv = (dw if Kpad == KP else dw[:, :KP].contiguous()).view(conv_w.shape)

@@ -327,7 +327,9 @@ def attn_pooled_bwd(q, kv, out, dout, lse, rows, B, L, H, causal, scale, seq_off
 
 # ---- embeddings / pooling ----------------------------------------------------------------------------------
 def _chk_keep(keep, B, G, name="keep"):
-    """int32 [B, K] device tensor of kept patch indices (1 <= K <= G) -> (ptr, K)"""
+    """int32 [B, K] device tensor of kept patch indices (1 <= K <= G) -> (ptr, K); None = every patch in grid order -> (0, G)"""
+    if keep is None:
+        return 0, G
     if keep.dim() != 2 or keep.shape[0] != B or not 1 <= keep.shape[1] <= G:
         raise RuntimeError(f"open_clip_amd: '{name}' must be int32 [B = {B}, K] with 1 <= K <= {G} (got {tuple(keep.shape)})")
     return _chk(keep, torch.int32, name), keep.shape[1]
@@ -359,14 +361,9 @@ def patchify(image, P, Kpad, keep=None):
     if Cin != 3:
         raise RuntimeError("patchify: images must have 3 channels")
     is16 = image.dtype == BF16
-    G = (H // P) * (W // P)
-    if keep is None:
-        out = empty((B * G, Kpad), BF16, image)
-        _lib.call("ocn_patchify", _chk(image, BF16 if is16 else F32, "image"), int(is16), _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
-        return out
-    kp, K = _chk_keep(keep, B, G)
+    kp, K = _chk_keep(keep, B, (H // P) * (W // P))
     out = empty((B * K, Kpad), BF16, image)
-    _lib.call("ocn_patchify_keep", _chk(image, BF16 if is16 else F32, "image"), int(is16), kp, K, _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
+    _lib.call("ocn_patchify", _chk(image, BF16 if is16 else F32, "image"), int(is16), kp, K, _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
     return out
 
 
@@ -379,53 +376,36 @@ def patchify_u8(image, P, Kpad, mean, std, hwc, keep=None):
     H, W = (image.shape[1], image.shape[2]) if hwc else (image.shape[2], image.shape[3])
     if (image.shape[3] if hwc else image.shape[1]) != 3:
         raise RuntimeError("patchify_u8: images must have 3 channels")
-    G = (H // P) * (W // P)
     m3, s3 = (ctypes.c_float * 3)(*[float(v) for v in mean]), (ctypes.c_float * 3)(*[float(v) for v in std])
-    if keep is None:
-        out = empty((B * G, Kpad), BF16, image)
-        _lib.call("ocn_patchify_u8", _chk(image, torch.uint8, "image"), int(hwc), m3, s3, _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
-        return out
-    kp, K = _chk_keep(keep, B, G)
+    kp, K = _chk_keep(keep, B, (H // P) * (W // P))
     out = empty((B * K, Kpad), BF16, image)
-    _lib.call("ocn_patchify_u8_keep", _chk(image, torch.uint8, "image"), int(hwc), m3, s3, kp, K, _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
+    _lib.call("ocn_patchify_u8", _chk(image, torch.uint8, "image"), int(hwc), m3, s3, kp, K, _chk(out, BF16, "patches"), B, H, W, P, Kpad, _stream())
     return out
 
 
-def embed_assemble_keep_fwd(patch_out, cls, pos, keep, B, G, C):
-    """emb fp32 [B * (K + 1), C]: class token + position 0, then patch_out[b*K + j] + pos[1 + keep[b, j]]"""
+def embed_assemble_fwd(patch_out, cls, pos, B, G, C, keep=None):
+    """emb fp32 [B * (K + 1), C]: class token + position 0, then patch_out[b*K + j] + pos[1 + keep[b, j]] (``keep`` None: all G patches in order)"""
     kp, K = _chk_keep(keep, B, G)
     if tuple(patch_out.shape) != (B * K, C) or tuple(pos.shape) != (G + 1, C) or cls.numel() != C:
-        raise RuntimeError("embed_assemble_keep_fwd: patch_out must be [B*K, C], pos [G+1, C], cls [C]")
+        raise RuntimeError("embed_assemble_fwd: patch_out must be [B*K, C], pos [G+1, C], cls [C]")
     emb = empty((B * (K + 1), C), F32, patch_out)
-    _lib.call("ocn_embed_assemble_keep_fwd", _chk(patch_out, F32, "patch_out"), _chk(cls, F32, "cls"), _chk(pos, F32, "pos"), kp,
+    _lib.call("ocn_embed_assemble_fwd", _chk(patch_out, F32, "patch_out"), _chk(cls, F32, "cls"), _chk(pos, F32, "pos"), kp,
               _chk(emb, F32, "emb"), B, G, K, C, _stream())
     return emb
 
 
-def embed_assemble_keep_bwd(demb, inv, dpos, dcls, B, G, K, C, deterministic=False, zero_dpatch=False):
-    """dpatch bf16 [B*K, C]; dpos [G+1, C] / dcls [C] are accumulated into (``inv`` int32 [B, G] from patch_keep_plan / patch_keep_inverse).
+def embed_assemble_bwd(demb, dpos, dcls, B, G, C, deterministic=False, inv=None, K=None, zero_dpatch=False):
+    """dpatch bf16 [B*K, C]; dpos [G+1, C] / dcls [C] are accumulated into (``inv`` int32 [B, G] from patch_keep_plan / patch_keep_inverse, with the
+    ``K`` of its keep; None: all G patches in order).
     The kernel reaches dpatch through ``inv`` alone: a row of ``keep`` that ``inv`` does not point back to (a caller's keep with a repeated or an
     out-of-range index) is never written.  ``zero_dpatch``: start from zeros, so that such a row adds nothing to the weight gradient (for an
     ``inv`` built from a caller's keep; the plan kernel's own ``inv`` covers every row)."""
-    if tuple(inv.shape) != (B, G) or tuple(demb.shape) != (B * (K + 1), C) or tuple(dpos.shape) != (G + 1, C) or dcls.numel() != C:
-        raise RuntimeError("embed_assemble_keep_bwd: demb must be [B*(K+1), C], inv [B, G], dpos [G+1, C], dcls [C]")
+    K = G if K is None else K
+    if (inv is not None and tuple(inv.shape) != (B, G)) or tuple(demb.shape) != (B * (K + 1), C) or tuple(dpos.shape) != (G + 1, C) or dcls.numel() != C:
+        raise RuntimeError("embed_assemble_bwd: demb must be [B*(K+1), C], inv [B, G], dpos [G+1, C], dcls [C]")
     dpatch = torch.zeros((B * K, C), dtype=BF16, device=demb.device) if zero_dpatch else empty((B * K, C), BF16, demb)
-    _lib.call("ocn_embed_assemble_keep_bwd", _chk(demb, F32, "demb"), _chk(inv, torch.int32, "inv"), _chk(dpatch, BF16, "dpatch"),
+    _lib.call("ocn_embed_assemble_bwd", _chk(demb, F32, "demb"), _chk(inv, torch.int32, "inv"), _chk(dpatch, BF16, "dpatch"),
               _chk(dpos, F32, "dpos"), _chk(dcls, F32, "dcls"), B, G, K, C, int(deterministic), _stream())
-    return dpatch
-
-
-def embed_assemble_fwd(patch_out, cls, pos, B, G, C):
-    emb = empty((B * (G + 1), C), F32, patch_out)
-    _lib.call("ocn_embed_assemble_fwd", _chk(patch_out, F32, "patch_out"), _chk(cls, F32, "cls"), _chk(pos, F32, "pos"),
-              _chk(emb, F32, "emb"), B, G, C, _stream())
-    return emb
-
-
-def embed_assemble_bwd(demb, dpos, dcls, B, G, C, deterministic=False):
-    dpatch = empty((B * G, C), BF16, demb)
-    _lib.call("ocn_embed_assemble_bwd", _chk(demb, F32, "demb"), _chk(dpatch, BF16, "dpatch"), _chk(dpos, F32, "dpos"),
-              _chk(dcls, F32, "dcls"), B, G, C, int(deterministic), _stream())
     return dpatch
 
 

@@ -118,3 +118,17 @@ def test_fixture_is_pinned_by_the_oracle():
     # every patch no image kept has a zero positional gradient in the reference, too
     never = sorted(set(range(36)) - set(g["keep"].reshape(-1).tolist()))
     assert all(float(p["visual.positional_embedding"].grad[1 + n].abs().max()) == 0.0 for n in never)
+
+
+@pytest.mark.parametrize("name,args", [
+    # keep / inv = 0 means every patch in grid order: K must then be G.  Operands are non-null dummies: the refusal comes before any launch or read.
+    ("ocn_embed_assemble_fwd", (64, 64, 64, 0, 64, 2, 36, 18, 128, 0)),            # K = 18, G = 36
+    ("ocn_embed_assemble_bwd", (64, 0, 64, 64, 64, 2, 36, 18, 128, 0, 0)),         # K = 18, G = 36
+    ("ocn_patchify", (64, 0, 0, 18, 64, 2, 96, 96, 16, 768, 0)),                   # K = 18, (96 / 16)^2 = 36
+])
+def test_dense_call_with_another_k_is_refused_on_the_host(name, args):
+    """argument validation happens before any launch (tests/test_cabi.py): safe without a GPU"""
+    from open_clip_amd import _lib, build
+    build.build()
+    with pytest.raises(RuntimeError, match=name + r": K=18 with G=36"):
+        _lib.call(name, *args)

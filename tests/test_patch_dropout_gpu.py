@@ -124,7 +124,7 @@ def test_assemble_keep_fwd(dev, C, K):
     gen = torch.Generator().manual_seed(C + K)
     po, cls, pos = torch.randn(B * K, C, generator=gen).to(dev), torch.randn(C, generator=gen).to(dev), torch.randn(G + 1, C, generator=gen).to(dev)
     keep = _random_keep(B, G, K, dev, 17)
-    emb = ops.embed_assemble_keep_fwd(po, cls, pos, keep, B, G, C)
+    emb = ops.embed_assemble_fwd(po, cls, pos, B, G, C, keep=keep)
     want = torch.cat([(cls + pos[0]).expand(B, 1, C), po.view(B, K, C) + pos[1 + keep.long()]], dim=1).reshape(B * (K + 1), C)
     assert torch.equal(emb, want)
 
@@ -151,14 +151,80 @@ def test_assemble_keep_bwd(dev, C, K):
     results = []
     for det in (False, True, True):
         dpos, dcls = torch.zeros(G + 1, C, device=dev), torch.zeros(C, device=dev)
-        dpatch = ops.embed_assemble_keep_bwd(demb, inv, dpos, dcls, B, G, K, C, deterministic=det)
+        dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, C, deterministic=det, inv=inv, K=K)
         assert torch.equal(dpatch.view(torch.int16), demb.view(B, K + 1, C)[:, 1:].reshape(B * K, C).bfloat16().view(torch.int16))
         e_pos, e_cls = (dpos.double() - ref).abs(), (dcls.double() - ref[0]).abs()
-        _report(f"embed_assemble_keep_bwd C={C} K={K} det={int(det)}: dpos max err/bound {float((e_pos / bound.clamp_min(1e-300)).max()):.3f} dcls {float((e_cls / bound[0]).max()):.3f}")
+        _report(f"embed_assemble_bwd with inv C={C} K={K} det={int(det)}: dpos max err/bound {float((e_pos / bound.clamp_min(1e-300)).max()):.3f} dcls {float((e_cls / bound[0]).max()):.3f}")
         assert bool((e_pos <= bound).all()) and bool((e_cls <= bound[0]).all())
         assert float(dpos[1 + never].abs().max()) == 0.0
         results.append((dpos, dcls))
     assert torch.equal(results[1][0], results[2][0]) and torch.equal(results[1][1], results[2][1])
+
+
+# ---- keep = None is the identity keep ----------------------------------------------------------------------------------------------------
+def _identity(B, G, dev):
+    return torch.arange(G, dtype=I32, device=dev).expand(B, G).contiguous()
+
+
+@pytest.mark.parametrize("size,P", [(96, 16), (112, 14)])
+@pytest.mark.parametrize("kind", ["fp32", "bf16", "u8_chw", "u8_hwc"])
+def test_patchify_identity_keep_is_the_dense_call(dev, size, P, kind):
+    """keep[b] = arange(G) against keep = None, bit for bit (the geometries of the row-gather test above: LDS fast path / generic uint8 kernel with padding)"""
+    from open_clip_amd import ops
+    B, G = 3, (size // P) ** 2
+    Kpad = (3 * P * P + 63) // 64 * 64
+    keep = _identity(B, G, dev)
+    gen = torch.Generator().manual_seed(6)
+    if kind in ("fp32", "bf16"):
+        img = torch.randn(B, 3, size, size, generator=gen).to(dev)
+        img = img.bfloat16() if kind == "bf16" else img
+        dense, got = ops.patchify(img, P, Kpad), ops.patchify(img, P, Kpad, keep=keep)
+    else:
+        hwc = kind == "u8_hwc"
+        img = torch.randint(0, 256, (B, size, size, 3) if hwc else (B, 3, size, size), generator=gen, dtype=torch.uint8).to(dev)
+        mean, std = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+        dense, got = ops.patchify_u8(img, P, Kpad, mean, std, hwc), ops.patchify_u8(img, P, Kpad, mean, std, hwc, keep=keep)
+    assert tuple(dense.shape) == tuple(got.shape) == (B * G, Kpad)
+    assert float(dense.float().abs().max()) > 0.0
+    assert torch.equal(got.view(torch.int16), dense.view(torch.int16))
+
+
+def test_assemble_fwd_identity_keep_is_the_dense_call(dev):
+    from open_clip_amd import ops
+    B, G, C = 5, 36, 128
+    gen = torch.Generator().manual_seed(31)
+    po, cls, pos = torch.randn(B * G, C, generator=gen).to(dev), torch.randn(C, generator=gen).to(dev), torch.randn(G + 1, C, generator=gen).to(dev)
+    dense = ops.embed_assemble_fwd(po, cls, pos, B, G, C)
+    got = ops.embed_assemble_fwd(po, cls, pos, B, G, C, keep=_identity(B, G, dev))
+    assert tuple(dense.shape) == (B * (G + 1), C) and torch.equal(got, dense)
+
+
+def test_assemble_bwd_identity_inv_is_the_dense_call(dev):
+    """B = 40: two batch chunks of the atomic form, the second ragged (8 images).  dpatch bit-equal in both modes; dpos / dcls bit-equal in the
+    deterministic form (a single writer in batch order); with atomics the two chunk sums arrive in either order, so each result is held to the
+    file's bound B * 2^-24 * sum |terms| around the float64 sum, and the two results to the same bound of each other."""
+    from open_clip_amd import ops
+    B, G, C = 40, 36, 128
+    inv = _identity(B, G, dev)
+    demb = torch.randn(B * (G + 1), C, generator=torch.Generator().manual_seed(41)).to(dev)
+    d3 = demb.view(B, G + 1, C).double()
+    ref, bound = d3.sum(0), B * 2.0 ** -24 * d3.abs().sum(0)
+    for det in (False, True):
+        out = []
+        for use_inv in (None, inv):
+            dpos, dcls = torch.zeros(G + 1, C, device=dev), torch.zeros(C, device=dev)
+            dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, C, deterministic=det, inv=use_inv, K=G)
+            out.append((dpatch, dpos, dcls))
+        (p0, pos0, cls0), (p1, pos1, cls1) = out
+        assert torch.equal(p0.view(torch.int16), p1.view(torch.int16))
+        assert torch.equal(p0.view(torch.int16), demb.view(B, G + 1, C)[:, 1:].reshape(B * G, C).bfloat16().view(torch.int16))
+        if det:
+            assert torch.equal(pos0, pos1) and torch.equal(cls0, cls1)
+        for dpos, dcls in ((pos0, cls0), (pos1, cls1)):
+            assert bool(((dpos.double() - ref).abs() <= bound).all()) and bool(((dcls.double() - ref[0]).abs() <= bound[0]).all())
+        d_pos, d_cls = (pos0.double() - pos1.double()).abs(), (cls0.double() - cls1.double()).abs()
+        _report(f"embed_assemble_bwd identity inv vs dense det={int(det)}: dpos max diff/bound {float((d_pos / bound).max()):.3f} dcls {float((d_cls / bound[0]).max()):.3f}")
+        assert bool((d_pos <= bound).all()) and bool((d_cls <= bound[0]).all())
 
 
 # ---- the whole step ----------------------------------------------------------------------------------------------------------------------

@@ -59,8 +59,9 @@ const char* ocn_last_error(void);
  *   105            patch dropout of the image tower: new ocn_patch_keep_plan, ocn_patch_keep_inverse, ocn_patchify_keep, ocn_patchify_u8_keep,
  *                  ocn_embed_assemble_keep_fwd, ocn_embed_assemble_keep_bwd (no signature changed).
  *   106            BREAKING: one entry point per image-embedding op.  ocn_patchify / ocn_patchify_u8 / ocn_embed_assemble_fwd take a nullable `keep` and K,
- *                  ocn_embed_assemble_bwd a nullable `inv` and K; the four `_keep` twins of 105 are gone. */
-#define OCN_ABI_VERSION 106
+ *                  ocn_embed_assemble_bwd a nullable `inv` and K; the four `_keep` twins of 105 are gone.
+ *   107            CLIPA towers (mean-pooled image tower without ln_pre): new ocn_mean_pool_fwd, ocn_mean_pool_bwd, ocn_cast_bf16_f32 (no signature changed). */
+#define OCN_ABI_VERSION 107
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -115,6 +116,10 @@ int ocn_gemm_tn_accum_det(const void* A, int lda, const void* B, int ldb, float*
 /* ---- casts -------------------------------------------------------------------------------------
  * amp_bf16 policy (precision.py:6-16): fp32 master weights, bf16 GEMM operands. */
 int ocn_cast_f32_bf16(const float* src, void* dst, int64_t n, ocn_stream_t stream);
+/* the widening twin, dst fp32 = src bf16 (exact).  An image tower built with `no_ln_pre` (nn.Identity at transformer.py:660) has no LayerNorm backward
+ * in front of its embedding that would hand the bf16 stream's gradient on in fp32: this cast does, once per step (autograd of transformer.py:794-808
+ * under autocast, where the gradient of conv1's bf16 output is widened by the cast's own backward).  src, dst 16-byte aligned; any n > 0. */
+int ocn_cast_bf16_f32(const void* src, float* dst, int64_t n, ocn_stream_t stream);
 /* dst = bf16(src * *scale_dev): the scalar is read on the device, so a caller that holds it in a tensor (logit_scale.exp(),
  * loss.py:103-110) never has to synchronise the host to pass it */
 int ocn_cast_f32_bf16_scaled(const float* src, void* dst, int64_t n, const float* scale_dev, ocn_stream_t stream);
@@ -273,6 +278,16 @@ int ocn_scatter_rows(const float* d, const int32_t* idx, float* dx, void* dx_bf1
  * into the all-row LayerNorm backward's result instead of travelling through a zero [M, C] residual-gradient matrix.  dx = NULL (bf16
  * gradient stream): dx_bf16[row_b] = bf16(dx_bf16[row_b] + d[b]). */
 int ocn_scatter_add_rows(const float* d, const int32_t* idx, float* dx, void* dx_bf16, int B, int L, int C, ocn_stream_t stream);
+
+/* ---- mean pooling ('avg': `x[:, 1:].mean(dim=1)`, transformer.py:783-785; the CLIPA image towers) ----------------------------
+ * fwd: out[b, c] = (sum_{t = skip .. T-1} x[b*T + t, c]) / float(T - skip); x [B*T, C] fp32 or bf16 (x_is_bf16), out fp32 [B, C].  fp32 accumulation in
+ *      one fixed order (the tokens of an image dealt out over the waves of a workgroup, the partial sums added in wave order), then ONE correctly
+ *      rounded fp32 division: bit-reproducible, and exact whenever the sum is.  Rows t < skip are never read.
+ * bwd: autograd of the same line: every row of [B*T, C] is written -- rows t < skip exact zeros, the others dpooled[b, c] / float(T - skip) -- as fp32
+ *      (dx), as its round-to-nearest-even bf16 (dx_bf16), or both in one pass; either pointer may be NULL, not both.  Nothing has to be zeroed first.
+ * Checked on the host before any launch: no null operand, B, C > 0, 0 <= skip < T, C % 8 == 0, 16-byte aligned operands. */
+int ocn_mean_pool_fwd(const void* x, int x_is_bf16, float* out, int B, int T, int skip, int C, ocn_stream_t stream);
+int ocn_mean_pool_bwd(const float* dpooled, float* dx, void* dx_bf16, int B, int T, int skip, int C, ocn_stream_t stream);
 
 /* ---- F.normalize (model.py:391,411; eps 1e-12) -------------------------------------------------
  * fwd: y = x / max(||x||, eps) as fp32 and bf16, inv_norm[B] saved; bwd: dx = (dy - y*(y.dy)) * inv_norm */

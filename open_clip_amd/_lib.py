@@ -24,6 +24,7 @@ SIGNATURES = {
     "ocn_sub_scaled_rows": [_p, _i, _p, _i, _p, _f, _i, _i, _p],
     "ocn_cast_f32_bf16": [_p, _p, _l, _p],
     "ocn_cast_f32_bf16_scaled": [_p, _p, _l, _p, _p],
+    "ocn_cast_bf16_f32": [_p, _p, _l, _p],
     "ocn_cast_transpose_f32_bf16": [_p, _p, _i, _i, _p],
     "ocn_layernorm_fwd": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p],
     "ocn_layernorm_bwd": [_p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p],
@@ -56,6 +57,8 @@ SIGNATURES = {
     "ocn_gather_rows_bf16": [_p, _p, _p, _i, _i, _i, _p],
     "ocn_scatter_rows": [_p, _p, _p, _p, _i, _i, _i, _p],
     "ocn_scatter_add_rows": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "ocn_mean_pool_fwd": [_p, _i, _p, _i, _i, _i, _i, _p],
+    "ocn_mean_pool_bwd": [_p, _p, _p, _i, _i, _i, _i, _p],
     "ocn_l2norm_fwd": [_p, _p, _p, _p, _i, _i, _f, _p],
     "ocn_l2norm_bwd": [_p, _p, _p, _p, _i, _i, _p],
     "ocn_softmax_ce_rows": [_p, _i, _p, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p],
@@ -91,7 +94,7 @@ DEBUG_SIGNATURES = {
 _SPECIAL = {"ocn_last_error": ([], ctypes.c_char_p), "ocn_version": ([], _i), "ocn_gemm_tn_det_workspace_bytes": ([_i, _i, _i], _l),
             "ocn_fused_logits_ce_workspace_floats": ([_i, _i], _l), "ocn_gemm_nt_splitk_plan": ([_i, _i, _i], _i), "ocn_layernorm_bwd_det_workspace_floats": ([_i, _i], _l), "ocn_get_tile_rescue": ([], _i)}
 
-ABI_VERSION = 106  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
+ABI_VERSION = 107  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
 
 _lib = None
 _lock = threading.Lock()

@@ -6,8 +6,10 @@ Mirrors the reference's JSON registry (``src/open_clip/model_configs/*.json``, l
 (``CLIPVisionCfg.head_width = 64`` model.py:37-60, ``CLIPTextCfg`` model.py:108-150).
 Registered: every ``ViT-*`` config of the reference whose towers are the plain pre-LN ViT + causal text transformer this path implements
 (learnable position embedding, class-token pooling, argmax text pooling, nn.GELU or QuickGELU; head_dim a multiple of 8 up to 128) -- the BASELINE
-models (ViT-B-32, ViT-L-14, ViT-H-14) and their size / resolution variants -- plus tiny ones for parity tests.  SigLIP / CoCa / timm / HF
-configs need other blocks (attentional pooling, no class token, other tokenisers) and are rejected by ``NativeCLIP._check_cfg`` if added.
+models (ViT-B-32, ViT-L-14, ViT-H-14) and their size / resolution variants -- and the six ``ViT-*-CLIPA`` configs, the one other family the reference
+builds from the same two classes: image tower without ln_pre, mean pooling over the patch tokens in front of ln_post, text tower of context 32 without
+a causal mask, pooled at its last position (``_clipa`` below) -- plus tiny ones for parity tests.  SigLIP / CoCa / timm / HF
+configs need other blocks (attentional pooling, no class token, HF text towers) and are rejected by ``NativeCLIP._check_cfg`` if added.
 """
 import copy
 import json
@@ -43,6 +45,27 @@ _REFERENCE_VITS = {
     # head_dim 88 / 104 / 112 and the MLP widths 6144 / 8192 / 15360 (int(width * mlp_ratio), transformer.py:283)
     "ViT-g-14": (1024, 224, 40, 1408, 14, 1024, 16, 24, 88, 4.3637), "ViT-bigG-14": (1280, 224, 48, 1664, 14, 1280, 20, 32, 104, 4.9231),
     "ViT-e-14": (1280, 224, 56, 1792, 14, 1280, 20, 36, 112, 8.5715),
+}
+
+
+def _clipa(embed, image, layers, width, t_width, t_heads, t_layers, head_width=None, mlp_ratio=None):
+    """src/open_clip/model_configs/ViT-*-CLIPA*.json: patch 14; `no_ln_pre`, 'avg' pooling, `final_ln_after_pool` (transformer.py:660, :783-785, :826-828);
+    text: context 32, vocabulary 32000 (a BERT tokenizer: those keys never reach the model), `no_causal_mask`, 'last' pooling (:939-940)"""
+    v = {"image_size": image, "layers": layers, "width": width, "patch_size": 14, "no_ln_pre": True, "pool_type": "avg", "final_ln_after_pool": True}
+    if head_width is not None:
+        v["head_width"] = head_width
+    if mlp_ratio is not None:
+        v["mlp_ratio"] = mlp_ratio
+    t = {"context_length": 32, "vocab_size": 32000, "hf_tokenizer_name": "bert-base-uncased", "tokenizer_kwargs": {"strip_sep_token": True},
+         "width": t_width, "heads": t_heads, "layers": t_layers, "pool_type": "last", "no_causal_mask": True}
+    return {"embed_dim": embed, "vision_cfg": v, "text_cfg": t}
+
+
+# name: (embed_dim, image_size, vision layers, vision width, text width, text heads, text layers[, head_width[, mlp_ratio]])
+_REFERENCE_CLIPA = {
+    "ViT-L-14-CLIPA": (768, 224, 24, 1024, 768, 12, 12), "ViT-L-14-CLIPA-336": (768, 336, 24, 1024, 768, 12, 12),
+    "ViT-H-14-CLIPA": (1024, 224, 32, 1280, 1024, 16, 24, 80), "ViT-H-14-CLIPA-336": (1024, 336, 32, 1280, 1024, 16, 24, 80),
+    "ViT-bigG-14-CLIPA": (1280, 224, 48, 1664, 1280, 20, 32, 104, 4.9231), "ViT-bigG-14-CLIPA-336": (1280, 336, 48, 1664, 1280, 20, 32, 104, 4.9231),
 }
 _REFERENCE_QUICKGELU = ("ViT-B-16", "ViT-L-14", "ViT-L-14-336", "ViT-H-14", "ViT-H-14-378", "ViT-bigG-14")  # <name>-quickgelu.json twins
 
@@ -91,6 +114,12 @@ _MODEL_CONFIGS = {
         "vision_cfg": {"image_size": 70, "layers": 1, "width": 352, "head_width": 88, "mlp_ratio": 4.3637, "patch_size": 14},
         "text_cfg": {"context_length": 77, "vocab_size": 1024, "width": 128, "heads": 2, "layers": 2},
     },
+    # the CLIPA shape in miniature (G = 16 patches, T = 17): no ln_pre, mean pooling in front of ln_post; bidirectional text pooled at its last position
+    "tiny-clipa-test": {
+        "embed_dim": 64,
+        "vision_cfg": {"image_size": 64, "layers": 2, "width": 128, "patch_size": 16, "no_ln_pre": True, "pool_type": "avg", "final_ln_after_pool": True},
+        "text_cfg": {"context_length": 16, "vocab_size": 512, "width": 128, "heads": 2, "layers": 2, "pool_type": "last", "no_causal_mask": True},
+    },
     "small-test": {
         "embed_dim": 128,
         "vision_cfg": {"image_size": 96, "layers": 2, "width": 256, "patch_size": 16},
@@ -101,6 +130,8 @@ _MODEL_CONFIGS = {
 
 for _name, _dims in _REFERENCE_VITS.items():
     _MODEL_CONFIGS[_name] = _vit(*_dims)
+for _name, _dims in _REFERENCE_CLIPA.items():
+    _MODEL_CONFIGS[_name] = _clipa(*_dims)
 for _name in _REFERENCE_QUICKGELU:
     _MODEL_CONFIGS[_name + "-quickgelu"] = dict(copy.deepcopy(_MODEL_CONFIGS[_name]), quick_gelu=True)
 
@@ -153,13 +184,14 @@ def vision_tokens(cfg: dict, patch_dropout=None) -> int:
 
 def count_params(cfg: dict) -> int:
     v, t, e = cfg["vision_cfg"], cfg["text_cfg"], cfg["embed_dim"]
+    ln_pre = 0 if v.get("no_ln_pre") else 2 * v["width"]
 
     def tower(width, layers):
         per = 4 * width + 3 * width * width + 3 * width + width * width + width + 8 * width * width + 5 * width
         return layers * per
 
     n = tower(v["width"], v["layers"]) + tower(t["width"], t["layers"])
-    n += v["width"] * 3 * v["patch_size"] ** 2 + v["width"] + vision_tokens(cfg) * v["width"] + 4 * v["width"] + v["width"] * e
+    n += v["width"] * 3 * v["patch_size"] ** 2 + v["width"] + vision_tokens(cfg) * v["width"] + ln_pre + 2 * v["width"] + v["width"] * e
     n += t["vocab_size"] * t["width"] + t["context_length"] * t["width"] + 2 * t["width"] + t["width"] * e + 1
     return n
 

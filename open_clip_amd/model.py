@@ -491,9 +491,15 @@ class _VisionEmbedFn(torch.autograd.Function):
         if keep is not None and inv is None and any(ctx.needs_input_grad):
             inv = ops.patch_keep_inverse(keep, G)
         bf = ex.stream != "fp32"  # bf16 residual stream: ln_pre hands its result on in bf16 (layers.py:23-26 under autocast); emb itself stays fp32 here
-        x16, x0, mean, rstd = ops.layernorm_fwd(emb, lnw, lnb, want_bf16=bf, want_f32=not bf)
-        x0 = x16 if bf else x0
-        ctx.save_for_backward(patches, emb, mean, rstd, lnw, conv_w, cls, pos)
+        if lnw is None:
+            # `no_ln_pre` (nn.Identity at transformer.py:660; the CLIPA towers): the assembled fp32 embedding IS the stream, or its ONE rounding to bf16
+            # (the reference's autocast rounds conv1's output, the class token and the positions separately and adds in bf16)
+            x0 = ops.cast_bf16(emb) if bf else emb
+            ctx.save_for_backward(patches, None, None, None, None, conv_w, cls, pos)
+        else:
+            x16, x0, mean, rstd = ops.layernorm_fwd(emb, lnw, lnb, want_bf16=bf, want_f32=not bf)
+            x0 = x16 if bf else x0
+            ctx.save_for_backward(patches, emb, mean, rstd, lnw, conv_w, cls, pos)
         ctx.meta = (B, G, K, width, KP, Kpad)
         ctx.keep, ctx.inv = keep, inv
         ctx.det = ex.deterministic
@@ -503,11 +509,15 @@ class _VisionEmbedFn(torch.autograd.Function):
     def backward(ctx, dx0):
         patches, emb, mean, rstd, lnw, conv_w, cls, pos = ctx.saved_tensors
         B, G, K, width, KP, Kpad = ctx.meta
-        dev = emb.device
-        dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
+        dev = patches.device
         dy0 = (_take_f32(dx0) if dx0.dtype == BF16 else None)  # bf16 stream: the first block's fp32 companion when there is one
         dy0 = dx0.contiguous() if dy0 is None else dy0
-        demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.det)
+        if lnw is None:  # no ln_pre: the stream's gradient is the embedding's, widened once when it arrives in bf16; no LayerNorm gradients exist
+            dlnw = dlnb = None
+            demb = ops.cast_f32(dy0) if dy0.dtype == BF16 else dy0
+        else:
+            dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
+            demb, _ = ops.layernorm_bwd(dy0, emb, lnw, mean, rstd, dlnw, dlnb, want_f32=True, deterministic=ctx.det)
         dpos, dcls = torch.zeros_like(pos), torch.zeros_like(cls)
         dpatch = ops.embed_assemble_bwd(demb, dpos, dcls, B, G, width, ctx.det, inv=ctx.inv, K=K, zero_dpatch=not ctx.own_plan)
         dw = torch.zeros(width, Kpad, dtype=F32, device=dev)
@@ -596,12 +606,15 @@ class _TextPack:
 # ------------------------------------------------------------------------------------------------------
 # pooled head: LN on the pooled token only (== LN on all tokens then pool), projection, F.normalize
 #   vision: transformer.py:829-831 + :923 ; text: model.py:403-411 + transformer.py:941-944
+#   'avg' with final_ln_after_pool (transformer.py:783-785, :826-828; the CLIPA image towers): the pooled row is the MEAN of the patch tokens and ln_post
+#   runs on it -- only the two ends differ (ocn_mean_pool_fwd instead of the gather, ocn_mean_pool_bwd instead of zero-fill + scatter)
 # ------------------------------------------------------------------------------------------------------
 class _HeadFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, lnw, lnb, proj, rows, ex, B, normalize):
-        """``rows`` (int32 [B]): absolute row of each sequence's pooled token in ``x``"""
-        pooled = ops.gather_rows(x, rows, B, 0)
+    def forward(ctx, x, lnw, lnb, proj, rows, ex, B, normalize, mean_T=None):
+        """``rows`` (int32 [B]): absolute row of each sequence's pooled token in ``x``; None: the pooled row of sequence b is the mean over the tokens
+        1 .. mean_T - 1 of its ``mean_T`` rows (the class token excluded)"""
+        pooled = ops.gather_rows(x, rows, B, 0) if rows is not None else ops.mean_pool_fwd(x, B, mean_T, 1)
         p16, _, mean, rstd = ops.layernorm_fwd(pooled, lnw, lnb)
         E = proj.shape[1]
         feat = ops.gemm_nt(ops.EPI_F32, p16, ex.cache.get(proj, "t"), ops.empty((B, E), F32, x))
@@ -610,13 +623,13 @@ class _HeadFn(torch.autograd.Function):
         else:
             y, inv = feat, None
         ctx.save_for_backward(pooled, p16, mean, rstd, lnw, proj, rows, y, inv)
-        ctx.meta = (ex, B, normalize, x.shape, x.dtype)
+        ctx.meta = (ex, B, normalize, x.shape, x.dtype, mean_T)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         pooled, p16, mean, rstd, lnw, proj, rows, y, inv = ctx.saved_tensors
-        ex, B, normalize, xshape, xdtype = ctx.meta
+        ex, B, normalize, xshape, xdtype, mean_T = ctx.meta
         none = [None] * (len(ctx.needs_input_grad) - 4)
         dy = dy.contiguous().float()
         dfeat = ops.l2norm_bwd(dy, y, inv) if normalize else dy
@@ -629,6 +642,15 @@ class _HeadFn(torch.autograd.Function):
         dlnw, dlnb = torch.zeros_like(lnw), torch.zeros_like(lnw)
         dcol = torch.zeros_like(lnw)  # column sums of dpooled = of dx (zero elsewhere): the last block's c_proj bias gradient, in fp32
         dpooled, _ = ops.layernorm_bwd(dp32, pooled, lnw, mean, rstd, dlnw, dlnb, want_f32=True, dcol=dcol, deterministic=ex.deterministic)
+        if rows is None:
+            # mean pooling: every patch row receives dpooled / (T - 1), the class rows zeros, in one pass that writes every row (nothing to clear);
+            # the column sums of dx are those of dpooled (T - 1 rows at weight 1 / (T - 1)), so dcol serves the last block as it does below
+            dx, dx16 = ops.mean_pool_bwd(dpooled, B, mean_T, 1, want_f32=xdtype != BF16, want_bf16=True)
+            if xdtype == BF16:
+                _publish_f32(dx16, None, dcol)
+                return (dx16, dlnw, dlnb, dproj, *none)
+            _publish_twin(dx, dx16, dcol)
+            return (dx, dlnw, dlnb, dproj, *none)
         dx16 = torch.zeros(xshape, dtype=BF16, device=dy.device)  # bf16 twin for the last block's dgrad / wgrad GEMMs
         if xdtype == BF16:  # all rows of a bf16 residual stream (full last block): the gradient itself is the bf16 tensor
             ops.scatter_rows(dpooled, rows, None, B, 0, dx16)
@@ -795,14 +817,19 @@ class Transformer(nn.Module):  # transformer.py:476-585
 
 
 def _pooled_last_block_ok(module) -> bool:
-    """the pooled form of the last block (see _PooledBlockFn) unless switched off on the module"""
-    return bool(getattr(module, "pooled_last_block", True))
+    """the pooled form of the last block (see _PooledBlockFn) unless switched off on the module; never for a mean-pooled tower, whose head reads
+    every row of the last block"""
+    return bool(getattr(module, "pooled_last_block", True)) and getattr(module, "pool_type", "tok") != "avg"
 
 
 def _tower_features(transformer, x, ex, B, L, causal, seq_off, rows, seq, pooled, ln, proj, normalize):
     """the residual blocks of a tower and its pooled head (_HeadFn).  ``rows`` (int32 [B]): absolute row of each sequence's pooled token in ``x``;
     ``pooled``: the last block runs behind its attention on those rows alone and hands on [B, C] -- sequence b in row b (``seq`` = arange(B), or None:
-    made here) -- instead of [M, C], where the head gathers ``rows`` itself"""
+    made here) -- instead of [M, C], where the head gathers ``rows`` itself.  ``rows`` None: mean pooling over the tokens 1 .. L - 1 of every sequence
+    (every row of the last block is read: never the pooled form)"""
+    if rows is None:
+        x = transformer(x, ex, B, L, causal, seq_off)
+        return _HeadFn.apply(x, ln.weight, ln.bias, proj, None, ex, B, normalize, L)
     if pooled:
         x = transformer(x, ex, B, L, causal, seq_off, rows)
         rows = seq if seq is not None else torch.arange(B, device=x.device, dtype=torch.int32)
@@ -869,8 +896,16 @@ class PatchDropout(nn.Module):  # transformer.py:17-58 (https://arxiv.org/abs/22
 
 
 class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: learnable pos, 'tok' pool)
-    def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, quick_gelu=False, patch_dropout=0.0):
+    def __init__(self, image_size, patch_size, width, layers, heads, mlp_ratio, output_dim, quick_gelu=False, patch_dropout=0.0,
+                 no_ln_pre=False, pool_type="tok", final_ln_after_pool=False):
+        """``no_ln_pre`` / ``pool_type`` / ``final_ln_after_pool``: transformer.py:608-611.  Implemented: 'tok' (ln_post before or after the pooling is the
+        same arithmetic: LayerNorm is per row) and 'avg' with ``final_ln_after_pool`` (the mean of the patch tokens, then ln_post: the CLIPA towers)."""
         super().__init__()
+        if pool_type not in ("tok", "avg") or (pool_type == "avg" and not final_ln_after_pool):
+            raise NotImplementedError(f"VisionTransformer: pool_type = {pool_type!r} with final_ln_after_pool = {final_ln_after_pool!r} is not implemented "
+                                      "('tok', or 'avg' together with final_ln_after_pool)")
+        self.pool_type = pool_type
+        self.final_ln_after_pool = bool(final_ln_after_pool)
         patch_dropout = 0.0 if patch_dropout is None else patch_dropout
         if not 0 <= patch_dropout < 1:
             raise ValueError(f"patch_dropout must satisfy 0 <= prob < 1 (got {patch_dropout!r})")
@@ -886,7 +921,7 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
         self.conv1 = _Conv1(width, patch_size)
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn(self.grid_size[0] * self.grid_size[1] + 1, width))
-        self.ln_pre = LayerNorm(width)
+        self.ln_pre = nn.Identity() if no_ln_pre else LayerNorm(width)  # transformer.py:660: no parameters, no `visual.ln_pre.*` keys
         self.transformer = Transformer(width, layers, heads, mlp_ratio, quick_gelu)
         self.ln_post = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
@@ -954,8 +989,11 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
             pd.last_keep = keep
         T = (G if keep is None else keep.shape[1]) + 1
         drop = () if keep is None else (keep, inv)  # without a plan the call is the one it always was
+        lnw, lnb = (self.ln_pre.weight, self.ln_pre.bias) if isinstance(self.ln_pre, LayerNorm) else (None, None)
         x = _VisionEmbedFn.apply(image, self.conv1.weight, self.class_embedding, self.positional_embedding,
-                                 self.ln_pre.weight, self.ln_pre.bias, ex, self.patch_size[0], norm, *drop)
+                                 lnw, lnb, ex, self.patch_size[0], norm, *drop)
+        if self.pool_type == "avg":  # the mean over the T - 1 patch tokens the tower ran (the kept ones under patch dropout / a caller's keep)
+            return _tower_features(self.transformer, x, ex, B, T, False, None, None, None, False, self.ln_post, self.proj, normalize)
         seq = torch.arange(B, device=x.device, dtype=torch.int32)
         rows = seq * T  # the class token of every image
         return _tower_features(self.transformer, x, ex, B, T, False, None, rows, seq, _pooled_last_block_ok(self), self.ln_post, self.proj, normalize)
@@ -965,24 +1003,40 @@ ATTENTION_HEAD_DIMS = (64, 80, 88, 96, 104, 112, 128)  # instantiations of csrc/
 
 
 class NativeCLIP(nn.Module):
-    """Drop-in for ``open_clip.model.CLIP`` (model.py:318-548) on the ViT + causal-text path."""
+    """Drop-in for ``open_clip.model.CLIP`` (model.py:318-548) on the ViT + text-transformer path: class-token image pooling behind a causal,
+    argmax-pooled text tower (the ``ViT-*`` configs), or the CLIPA shape -- image tower without ln_pre, mean-pooled in front of ln_post, text tower
+    without a mask, pooled at its last position."""
 
     # options of the reference's CLIPVisionCfg / CLIPTextCfg / CLIP.__init__ (model.py:27-131, :318-365) that the native path implements,
     # with the only value it implements for the others (the reference dataclass default): anything else must fail loudly instead of
     # training a silently different model (e.g. a *-quickgelu config or a SigLIP-style pooling registered through add_model_config)
     _VISION_KEYS = {"layers", "width", "head_width", "mlp_ratio", "patch_size", "image_size", "patch_dropout"}
     _TEXT_KEYS_OK = {"context_length", "vocab_size", "width", "heads", "layers", "mlp_ratio"}
-    _VISION_DEFAULTS = {"ls_init_value": None, "attentional_pool": False, "pos_embed_type": "learnable", "no_ln_pre": False,
-                        "pool_type": "tok", "final_ln_after_pool": False, "output_tokens": False, "act_kwargs": None, "norm_kwargs": None,
+    _VISION_DEFAULTS = {"ls_init_value": None, "attentional_pool": False, "pos_embed_type": "learnable",
+                        "output_tokens": False, "act_kwargs": None, "norm_kwargs": None,
                         "block_type": None, "qk_norm": False, "scaled_cosine_attn": False, "scale_heads": False, "scale_attn_inner": False,
                         "scale_attn": False, "scale_fc": False, "timm_model_name": None, "in_chans": 3}
-    _TEXT_DEFAULTS = {"hf_model_name": None, "hf_tokenizer_name": None, "tokenizer_kwargs": None, "tokenizer_mode": None, "ls_init_value": None,
-                      "embed_cls": False, "pad_id": 0, "eos_id": None, "no_causal_mask": False, "final_ln_after_pool": False, "pool_type": "argmax",
+    _TEXT_DEFAULTS = {"hf_model_name": None, "ls_init_value": None,
+                      "embed_cls": False, "pad_id": 0, "eos_id": None, "final_ln_after_pool": False,
                       "proj_bias": False, "proj_type": "linear", "output_tokens": False, "act_kwargs": None, "norm_kwargs": None, "block_type": None,
                       "qk_norm": False, "scaled_cosine_attn": False, "scale_heads": False, "scale_attn_inner": False, "scale_attn": False,
                       "scale_fc": False, "mlp_type": "mlp", "hf_proj_type": None, "hf_pooler_type": None}
     _MODEL_DEFAULTS = {"cast_dtype": None, "nonscalar_logit_scale": False, "custom_text": False,
                        "multimodal_cfg": None}
+
+    # switches with more than one implemented value: key -> (cfg, value) -> implemented?  Exactly the combinations the reference registry ships
+    # (its ViT-* and *-CLIPA configs), not every generalisation: 'avg' pooling only in front of ln_post, an unmasked text tower only with 'last' pooling
+    _SWITCHES = {
+        ("vision_cfg", "no_ln_pre"): lambda cfg, val: val is None or isinstance(val, bool),
+        ("vision_cfg", "final_ln_after_pool"): lambda cfg, val: val is None or isinstance(val, bool),
+        ("vision_cfg", "pool_type"): lambda cfg, val: val in (None, "tok") or (val == "avg" and cfg.get("final_ln_after_pool") is True),
+        ("text_cfg", "pool_type"): lambda cfg, val: val in (None, "argmax", "last"),
+        ("text_cfg", "no_causal_mask"): lambda cfg, val: not val or cfg.get("pool_type") == "last",
+        # the tokenizer's business (factory.py:91-151): they never reach the model
+        ("text_cfg", "hf_tokenizer_name"): lambda cfg, val: True,
+        ("text_cfg", "tokenizer_kwargs"): lambda cfg, val: True,
+        ("text_cfg", "tokenizer_mode"): lambda cfg, val: True,
+    }
 
     @classmethod
     def _check_cfg(cls, vision_cfg, text_cfg, model_kwargs):
@@ -993,6 +1047,12 @@ class NativeCLIP(nn.Module):
                     continue
                 if k in defaults and (val == defaults[k] or (val is None and not defaults[k])):
                     continue
+                if (name, k) in cls._SWITCHES:
+                    if cls._SWITCHES[(name, k)](cfg, val):
+                        continue
+                    raise NotImplementedError(f"NativeCLIP: {name}[{k!r}] = {val!r} is not implemented by the native path in this combination "
+                                              "(vision pool_type 'tok', or 'avg' with final_ln_after_pool; text pool_type 'argmax' or 'last', "
+                                              "no_causal_mask only with pool_type 'last')")
                 raise NotImplementedError(f"NativeCLIP: {name}[{k!r}] = {val!r} is not implemented by the native path "
                                           f"(supported: {sorted(ok)}; everything else only at the reference default)")
 
@@ -1028,7 +1088,8 @@ class NativeCLIP(nn.Module):
         # OpenAI / LAION-400M checkpoints)
         self.quick_gelu = bool(quick_gelu)
         self.visual = VisionTransformer(v["image_size"], v["patch_size"], v["width"], v["layers"], v["width"] // head_width,
-                                        v.get("mlp_ratio", 4.0), embed_dim, self.quick_gelu, v.get("patch_dropout", 0.0))
+                                        v.get("mlp_ratio", 4.0), embed_dim, self.quick_gelu, v.get("patch_dropout", 0.0),
+                                        bool(v.get("no_ln_pre")), v.get("pool_type") or "tok", bool(v.get("final_ln_after_pool")))
         tw = t["width"]
         self.transformer = Transformer(tw, t["layers"], t["heads"], t.get("mlp_ratio", 4.0), self.quick_gelu)
         self.context_length = t["context_length"]
@@ -1037,15 +1098,19 @@ class NativeCLIP(nn.Module):
         self.positional_embedding = nn.Parameter(torch.empty(self.context_length, tw).normal_(std=0.01))
         self.ln_final = LayerNorm(tw)
         self.text_projection = nn.Parameter(torch.empty(tw, embed_dim).normal_(std=tw ** -0.5))
-        self.text_pool_type = "argmax"
+        self.text_pool_type = t.get("pool_type") or "argmax"  # model.py:358; 'last' = x[:, -1] (transformer.py:939-940)
         self.text_eos_id = None
-        mask = torch.full((self.context_length, self.context_length), float("-inf")).triu_(1)
+        # `no_causal_mask` (transformer.py:1649): no mask at all -- every position attends to every position, padding included
+        self.text_causal = not t.get("no_causal_mask")
+        mask = torch.full((self.context_length, self.context_length), float("-inf")).triu_(1) if self.text_causal else None
         self.register_buffer("attn_mask", mask, persistent=False)  # model.py:360 (kept for API parity; kernels use a predicate)
         self.logit_scale = nn.Parameter(torch.ones([]) * init_logit_scale)
         self.logit_bias = nn.Parameter(torch.ones([]) * init_logit_bias) if init_logit_bias is not None else None
         self._cache = _WeightCache()
         # packed text tower (see _TextPack): on by default where the varlen attention kernels apply (head_dim 64, L <= 320);
         # ``pack_text = False`` runs every one of the context_length positions like the reference does
+        # The packed layout drops the positions behind the pooled EOT, which is only valid behind a causal mask with argmax pooling: a tower that
+        # pools its last position or attends without a mask runs dense, and ``pack_text`` reads False on it whatever is assigned (see the property)
         self.pack_text = bool(pack_text) and t["width"] // t["heads"] == 64 and self.context_length <= 320
         self.attn_buckets = bool(attn_buckets)
         self._tower_side = _StreamMap()  # device -> the image tower's stream (created on first use)
@@ -1064,6 +1129,14 @@ class NativeCLIP(nn.Module):
         # the bf16 operand copies are keyed by (address, version counter); writes through ``.data`` (checkpoint loading, EMA swaps,
         # manual re-initialisation) do not move the counter, so every load_state_dict drops them
         self.register_load_state_dict_post_hook(lambda module, incompatible: module.invalidate_weight_caches())
+
+    @property
+    def pack_text(self):
+        return self._pack_text and self.text_causal and self.text_pool_type == "argmax"
+
+    @pack_text.setter
+    def pack_text(self, value):
+        self._pack_text = bool(value)
 
     def invalidate_weight_caches(self):
         """drop the cached bf16 operand copies of the GEMM weights: call after writing to parameters through ``.data`` (anything that
@@ -1172,10 +1245,11 @@ class NativeCLIP(nn.Module):
             if int(ops.token_range_check(text.contiguous(), self.vocab_size)) != 0:
                 raise IndexError(f"index out of range in self: token id(s) outside [0, {self.vocab_size}) (token_embedding has {self.vocab_size} rows)")
             x = _TextEmbedFn.apply(text, self.token_embedding.weight, self.positional_embedding, None, ex)
-            idx = ops.argmax_rows(text.contiguous())
             seq_off, seq = None, torch.arange(B, device=x.device, dtype=torch.int32)
-            rows = seq * L + idx
-        return _tower_features(self.transformer, x, ex, B, L, True, seq_off, rows, seq, _pooled_last_block_ok(self), self.ln_final, self.text_projection, normalize)
+            # 'last': x[:, -1] (transformer.py:939-940); 'argmax': the EOT, the largest id (:941-944)
+            rows = seq * L + (L - 1) if self.text_pool_type == "last" else seq * L + ops.argmax_rows(text.contiguous())
+        return _tower_features(self.transformer, x, ex, B, L, self.text_causal, seq_off, rows, seq, _pooled_last_block_ok(self), self.ln_final,
+                               self.text_projection, normalize)
 
     def get_logits(self, image, text):
         """model.py:413-420: `logit_scale.exp() * image_features @ text_features.T` (+ logit_bias), and its transpose, through the library's own GEMM like

@@ -190,6 +190,13 @@ def cast_bf16_scaled(src, scale, out=None):
     return out
 
 
+def cast_f32(src, out=None):
+    """fp32 copy of a bf16 tensor (exact; ocn_cast_bf16_f32)"""
+    out = empty(src.shape, F32, src) if out is None else out
+    _lib.call("ocn_cast_bf16_f32", _chk(src, BF16, "src"), _chk(out, F32, "out"), src.numel(), _stream())
+    return out
+
+
 def cast_transpose_bf16(src, out=None):
     R, C = src.shape
     out = empty((C, R), BF16, src) if out is None else out
@@ -527,6 +534,30 @@ def scatter_add_rows(d, idx, dx, B, L, dx16=None):
     C = d.shape[1]
     _lib.call("ocn_scatter_add_rows", _chk(d, F32, "d"), _chk(idx, torch.int32, "idx"), _chk(dx, F32, "dx"), _chk(dx16, BF16, "dx16"), B, L, C, _stream())
     return dx
+
+
+def mean_pool_fwd(x, B, T, skip=1):
+    """fp32 [B, C]: the mean over the tokens ``skip .. T-1`` of every image of ``x`` [B*T, C] (fp32, or bf16: the image tower's bf16 residual stream);
+    fp32 sums in a fixed order and one correctly rounded division by ``T - skip`` (``x[:, 1:].mean(dim=1)`` with ``skip = 1``)"""
+    C = x.shape[1]
+    if x.dim() != 2 or x.shape[0] != B * T:
+        raise RuntimeError(f"mean_pool_fwd: x {tuple(x.shape)} is not [B*T = {B * T}, C]")
+    out = empty((B, C), F32, x)
+    x16 = x.dtype == BF16
+    _lib.call("ocn_mean_pool_fwd", _chk(x, BF16 if x16 else F32, "x"), int(x16), _chk(out, F32, "out"), B, T, int(skip), C, _stream())
+    return out
+
+
+def mean_pool_bwd(dpooled, B, T, skip=1, want_f32=True, want_bf16=True):
+    """(dx fp32 | None, dx bf16 | None), each [B*T, C] and written in full: zeros in the rows ``t < skip`` of every image, ``dpooled[b] / (T - skip)`` in
+    the others (the bf16 form is the rounding of the fp32 one)"""
+    if dpooled.dim() != 2 or dpooled.shape[0] != B or not (want_f32 or want_bf16):
+        raise RuntimeError(f"mean_pool_bwd: dpooled {tuple(dpooled.shape)} is not [B = {B}, C], or no output was asked for")
+    C = dpooled.shape[1]
+    dx = empty((B * T, C), F32, dpooled) if want_f32 else None
+    dx16 = empty((B * T, C), BF16, dpooled) if want_bf16 else None
+    _lib.call("ocn_mean_pool_bwd", _chk(dpooled, F32, "dpooled"), _chk(dx, F32, "dx"), _chk(dx16, BF16, "dx16"), B, T, int(skip), C, _stream())
+    return dx, dx16
 
 
 def l2norm_fwd(x, eps=1e-12):

@@ -85,6 +85,8 @@ def init_state_dict(cfg: dict, seed: int = 0, perturb: bool = False, siglip: boo
     sd["visual.proj"] = randn(vw, e, std=scale)
     sd["visual.conv1.weight"] = uniform(vw, 3, ps, ps, bound=1 / math.sqrt(3 * ps * ps))
     ln("visual.ln_pre", vw)
+    if v.get("no_ln_pre"):  # nn.Identity (transformer.py:660): no such keys -- drawn and dropped, so every other tensor keeps the values it always had
+        del sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"]
     for i in range(v["layers"]):
         block(f"visual.transformer.resblocks.{i}.", vw, int(vw * v.get("mlp_ratio", 4.0)))
     ln("visual.ln_post", vw)

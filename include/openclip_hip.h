@@ -60,8 +60,9 @@ const char* ocn_last_error(void);
  *                  ocn_embed_assemble_keep_fwd, ocn_embed_assemble_keep_bwd (no signature changed).
  *   106            BREAKING: one entry point per image-embedding op.  ocn_patchify / ocn_patchify_u8 / ocn_embed_assemble_fwd take a nullable `keep` and K,
  *                  ocn_embed_assemble_bwd a nullable `inv` and K; the four `_keep` twins of 105 are gone.
- *   107            CLIPA towers (mean-pooled image tower without ln_pre): new ocn_mean_pool_fwd, ocn_mean_pool_bwd, ocn_cast_bf16_f32 (no signature changed). */
-#define OCN_ABI_VERSION 107
+ *   107            CLIPA towers (mean-pooled image tower without ln_pre): new ocn_mean_pool_fwd, ocn_mean_pool_bwd, ocn_cast_bf16_f32 (no signature changed).
+ *   108            validation metrics (retrieval ranks, zero-shot top-k): new ocn_split_bf16x3, ocn_label_ranks (no signature changed). */
+#define OCN_ABI_VERSION 108
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -332,6 +333,26 @@ int ocn_sub_scaled_rows(float* out, int ldo, const void* x_bf16, int ldx, const 
 int ocn_siglip_rows(const float* logits, int ld, void* G, int ldg, int R, int N, int label_offset, int negative_only,
                     float bias, const float* bias_dev, float loss_scale, float grad_scale, float inv_logit_scale, float* loss_sum,
                     float* dscale_sum, float* dbias_sum, float* det_rows, ocn_stream_t stream);
+
+/* ---- validation metrics (open_clip_train/metrics.py:95-169 `_paired_retrieval_ranks`; open_clip_train/zero_shot.py:15-18 `accuracy`) ----
+ * ocn_label_ranks: Q bf16 [R, K] queries, C bf16 [N, K] candidates, both dense row-major (row stride K); labels int32 [R], every value in [0, N), or
+ *   NULL = paired retrieval, labels[r] = r (metrics.py:148-163; needs R <= N).  With the score s[r, j] = sum_k Q[r, k] * C[j, k] (fp32 accumulation on
+ *   v_mfma_f32_32x32x16_bf16; no score ever reaches memory) and the target t[r] = s[r, labels[r]]:
+ *     rank[r] = #{ j in [0, N) : s[r, j] > t[r]  or  (s[r, j] == t[r] and j < labels[r]) }      (int32 [R]; the tie rule of metrics.py:156-163)
+ *   Text -> image retrieval is the same call with the operands swapped; zero-shot top-k (`100 * features @ classifier` + topk, zero_shot.py:15-18,35-37)
+ *   is the same call with C = classifier^T, labels = the target class: a row is correct at k when rank < k.  A positive logit scale changes no rank and
+ *   is not an argument.
+ *   target fp32 [R]: workspace, holds t on return.  t comes out of the same tile routine and the same K order as every other score, so bit-identical
+ *   candidate rows (duplicate captions) score bit-identically and the index rule alone orders them.  Any R >= 1, N >= 1: rows past R write nothing, columns
+ *   past N are never counted.  A label outside [0, N) that only the device can see is clamped into the range (no access leaves a buffer).
+ *   Checked on the host before any launch: no null operand (labels excepted), R, N >= 1, K % 32 == 0, R <= N when labels == NULL, Q and C 16-byte
+ *   aligned, labels / target / rank 4-byte aligned.  Enqueues a clear of rank and two kernels; results do not vary from run to run (integer adds).
+ * ocn_split_bf16x3: the operands of the fp32 mode (`--val-retrieval-precision fp32`, metrics.py:14-21).  x fp32 [R, E] -> out bf16 [R, 3 * Ep], Ep = E rounded
+ *   up to a multiple of 32, every segment zero-padded: hi = bf16(x), lo = bf16(x - hi); role 0 (query) writes [hi | lo | hi], role 1 (candidate) writes
+ *   [hi | hi | lo], so ONE K = 3 * Ep product is hi.hi + lo.hi + hi.lo -- every term of the fp32 product but lo.lo (relative 2^-18).  The bf16 mode is
+ *   ocn_cast_f32_bf16 of the features.  x 4-byte, out 16-byte aligned; R, E >= 1. */
+int ocn_split_bf16x3(const float* x, void* out, int R, int E, int role, ocn_stream_t stream);
+int ocn_label_ranks(const void* Q, const void* C, const int32_t* labels, float* target, int32_t* rank, int R, int N, int K, ocn_stream_t stream);
 
 /* ---- optimizer (train.py:181-182, image_text_task.py:91-101) --------------
  * sumsq: out[0] += sum(x^2) (grad-norm for clip_grad_norm_);

@@ -5,6 +5,8 @@ Public surface (mirrors the reference names):
     NativeClipLoss, NativeSigLipLoss    <- open_clip.loss.ClipLoss / SigLipLoss
     get_model_config, add_model_config  <- open_clip.factory.get_model_config / add_model_config
     create_task, create_loss            <- open_clip.factory.create_task / create_loss (the reference's task classes around the native losses)
+    get_clip_metrics, zero_shot_accuracy, paired_retrieval_ranks, label_ranks
+                                        <- open_clip_train.metrics.get_clip_metrics / open_clip_train.zero_shot.accuracy (open_clip_amd.metrics)
 """
 from .configs import add_model_config, get_model_config, list_models  # noqa: F401
 
@@ -19,6 +21,9 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("create_task", "create_loss"):
         from . import factory
         return getattr(factory, name)
+    if name in ("get_clip_metrics", "zero_shot_accuracy", "paired_retrieval_ranks", "label_ranks"):
+        from . import metrics
+        return getattr(metrics, name)
     if name in ("NativeAdamW",):
         from . import optim
         return getattr(optim, name)

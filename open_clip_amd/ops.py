@@ -621,3 +621,58 @@ def adamw_step(w, g, m, v, lr, beta1, beta2, eps, weight_decay, step, w_bf16=Non
     _lib.call("ocn_adamw_step", _chk(w, F32, "w"), _chk(g, F32, "g"), _chk(m, F32, "m"), _chk(v, F32, "v"),
               _chk(w_bf16, BF16, "w_bf16"), w.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
               int(step), _chk(clip_coef, F32, "clip_coef"), _stream())
+
+
+# ---- validation metrics (open_clip_train/metrics.py, zero_shot.py) -------------------------------------------------
+def _on_gpu(t, dtype, name):
+    """device and dtype as ``_chk``; a strided view is made contiguous here (the rank kernels take dense rows only)"""
+    if not t.is_cuda:
+        raise RuntimeError(f"open_clip_amd: '{name}' must live on the MI355X (got {t.device}); there is no CPU path")
+    if t.dtype != dtype:
+        raise RuntimeError(f"open_clip_amd: '{name}' must be {dtype} (got {t.dtype})")
+    return t.contiguous()
+
+
+def split_bf16x3(x, role):
+    """fp32 [R, E] -> bf16 [R, 3 * Ep] (Ep = E rounded up to 32): hi = bf16(x), lo = bf16(x - hi); ``role`` "query" writes [hi | lo | hi], "candidate"
+    [hi | hi | lo] -- one product of the two is hi.hi + lo.hi + hi.lo (ocn_split_bf16x3)"""
+    if role not in ("query", "candidate"):
+        raise ValueError(f"split_bf16x3: role must be 'query' or 'candidate' (got {role!r})")
+    if x.dim() != 2:
+        raise RuntimeError("split_bf16x3: x must be 2-D")
+    x = _on_gpu(x, F32, "x")
+    R, E = x.shape
+    out = empty((R, 3 * ((E + 31) // 32 * 32)), BF16, x)
+    _lib.call("ocn_split_bf16x3", x.data_ptr(), out.data_ptr(), R, E, 0 if role == "query" else 1, _stream())
+    return out
+
+
+def pad_cast_bf16(x):
+    """fp32 [R, E] -> bf16 [R, Ep], zero-padded to a multiple of 32 columns: the one-segment operand of the bf16 rank mode (ocn_cast_f32_bf16)"""
+    if x.dim() != 2:
+        raise RuntimeError("pad_cast_bf16: x must be 2-D")
+    x = _on_gpu(x, F32, "x")
+    E = x.shape[1]
+    if E % 32:
+        x = torch.nn.functional.pad(x, (0, 32 - E % 32))
+    return cast_bf16(x)
+
+
+def label_ranks(q16, c16, labels=None, return_target=False):
+    """rank[r] = #{j : s[r, j] > t[r] or (s[r, j] == t[r] and j < labels[r])} with s = q16 @ c16^T in fp32 and t[r] = s[r, labels[r]] (ocn_label_ranks;
+    metrics.py:156-163).  q16 bf16 [R, K], c16 bf16 [N, K], K % 32 == 0; labels int32 [R] in [0, N) or None = arange(R).  Returns int32 [R] (and the fp32
+    targets, which leave the same tile routine as every other score)."""
+    if q16.dim() != 2 or c16.dim() != 2 or q16.shape[1] != c16.shape[1]:
+        raise RuntimeError(f"label_ranks: shape mismatch q{tuple(q16.shape)} c{tuple(c16.shape)}")
+    q16, c16 = _on_gpu(q16, BF16, "q16"), _on_gpu(c16, BF16, "c16")
+    R, K = q16.shape
+    N = c16.shape[0]
+    pl = 0
+    if labels is not None:
+        labels = _on_gpu(labels, torch.int32, "labels")
+        if labels.shape != (R,):
+            raise RuntimeError(f"label_ranks: labels must have shape ({R},), got {tuple(labels.shape)}")
+        pl = labels.data_ptr()
+    target, rank = empty((R,), F32, q16), empty((R,), torch.int32, q16)
+    _lib.call("ocn_label_ranks", q16.data_ptr(), c16.data_ptr(), pl, target.data_ptr(), rank.data_ptr(), R, N, K, _stream())
+    return (rank, target) if return_target else rank

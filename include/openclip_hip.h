@@ -61,8 +61,12 @@ const char* ocn_last_error(void);
  *   106            BREAKING: one entry point per image-embedding op.  ocn_patchify / ocn_patchify_u8 / ocn_embed_assemble_fwd take a nullable `keep` and K,
  *                  ocn_embed_assemble_bwd a nullable `inv` and K; the four `_keep` twins of 105 are gone.
  *   107            CLIPA towers (mean-pooled image tower without ln_pre): new ocn_mean_pool_fwd, ocn_mean_pool_bwd, ocn_cast_bf16_f32 (no signature changed).
- *   108            validation metrics (retrieval ranks, zero-shot top-k): new ocn_split_bf16x3, ocn_label_ranks (no signature changed). */
-#define OCN_ABI_VERSION 108
+ *   108            validation metrics (retrieval ranks, zero-shot top-k): new ocn_split_bf16x3, ocn_label_ranks (no signature changed).
+ *   109            BREAKING: one entry point per attention / token-embedding op.  ocn_attn_fwd / ocn_attn_bwd take head_dim and a nullable seq_off, order and
+ *                  bucket_counts (ocn_attn_bwd also delta_ws); ocn_token_embed_fwd takes a nullable posidx, ocn_token_embed_bwd is the sorted form with a
+ *                  nullable seq_off.  Gone: ocn_attn_{fwd,bwd}_hd, ocn_attn_{fwd,bwd}_varlen, ocn_token_embed_fwd_rows, ocn_token_embed_bwd_sorted[_varlen]
+ *                  and the unsorted per-occurrence-atomic ocn_token_embed_bwd. */
+#define OCN_ABI_VERSION 109
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -151,37 +155,29 @@ int ocn_layernorm_bwd(const void* dy, int dy_is_f32, const void* x, int x_is_bf1
 int64_t ocn_layernorm_bwd_det_workspace_floats(int M, int C);
 int ocn_colsum_f32(const float* x, float* out, int R, int C, int deterministic, ocn_stream_t stream);
 /* ---- attention core (transformer.py:199-244: head split + F.scaled_dot_product_attention) ------
- * qkv bf16 [B*L, 3*H*64] (q | k | v column blocks, heads contiguous inside each: the layout F.linear with
- * in_proj_weight produces, transformer.py:169); out bf16 [B*L, H*64]; lse fp32 [B*H*L] (natural log).
- * head_dim is 64; L <= 320.  causal != 0 applies the text tower's upper-triangular -inf mask
- * (transformer.py:1716-1722) as a predicate. */
-int ocn_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int causal, float scale,
-                 ocn_stream_t stream);
-int ocn_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int L, int H,
-                 int causal, float scale, ocn_stream_t stream);
-/* The same with an explicit head_dim (64, 80, 88, 96, 104, 112 or 128; qkv [B*L, 3*H*head_dim]): head_dim 64 up to 128 tokens (forward)
- * / 320 tokens (backward) runs the head-resident kernels above, everything else (ViT-H-14: head_dim 80, 257 tokens; ViT-L-14's 257 tokens;
- * ViT-g / bigG / e: head_dim 88 / 104 / 112) the STREAMED kernels of csrc/attention_generic.hip: 4-wave workgroups that own four 32-row
- * blocks and stream the operand all of them need through a two-slot LDS ring in 64-row chunks (18-35 KB of LDS per workgroup, any
- * sequence length).  The backward's workspace `delta_ws` is fp32 [B*H*L] (sum_d dO*O, exchanged between its launches; may be NULL on the
- * head-resident path). */
-int ocn_attn_fwd_hd(const void* qkv, void* out, float* lse, int B, int L, int H, int head_dim, int causal, float scale,
-                    ocn_stream_t stream);
-int ocn_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws, int B, int L,
-                    int H, int head_dim, int causal, float scale, ocn_stream_t stream);
-/* Packed ("varlen") batches, head_dim 64.  The text tower pools x[b, argmax(text[b])] (transformer.py:941-944) under the causal
- * mask (:1716-1722), so the tokens behind the pooled one cannot influence the feature or any gradient: the native text tower keeps
- * only the first eot[b]+1 tokens of each sequence.  Sequence b owns rows seq_off[b] .. seq_off[b+1] of qkv / out / dout / dqkv
- * (seq_off: B+1 ascending int32 on the device, 1 <= length <= Lmax <= 320); lse keeps the dense fp32 [B,H,Lmax] layout.
- * Bucketing (optional; both pointers or neither): `order` = the B sequence ids grouped by ceil(length / 32) ascending (DEVICE, from
- * ocn_seq_bucket_plan), `bucket_counts` = how many sequences each group holds (HOST array of ceil(Lmax / 32) ints summing to B).  One
- * launch per non-empty group, its workgroups sized for that group's length instead of Lmax (these kernels are latency-bound: their
- * rate is the number of resident workgroups); results do not depend on the bucketing. */
-int ocn_attn_fwd_varlen(const void* qkv, void* out, float* lse, const int32_t* seq_off, const int32_t* order, const int32_t* bucket_counts,
-                        int B, int Lmax, int H, int causal, float scale, ocn_stream_t stream);
-int ocn_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, const int32_t* seq_off,
-                        const int32_t* order, const int32_t* bucket_counts, int B, int Lmax, int H, int causal, float scale,
-                        ocn_stream_t stream);
+ * qkv bf16 [rows, 3*H*head_dim] (q | k | v column blocks, heads contiguous inside each: the layout F.linear with in_proj_weight produces,
+ * transformer.py:169); out bf16 [rows, H*head_dim]; lse fp32 [B*H*L] (natural log).  causal != 0 applies the text tower's upper-triangular
+ * -inf mask (transformer.py:1716-1722) as a predicate.
+ * Layout of the rows:
+ *   seq_off == NULL: a dense batch, sequence b owns rows b*L .. (b+1)*L.  order and bucket_counts must be NULL too.
+ *   seq_off != NULL: a packed ("varlen") batch.  The text tower pools x[b, argmax(text[b])] (transformer.py:941-944) under the causal mask, so the
+ *     tokens behind the pooled one cannot influence the feature or any gradient: the native text tower keeps only the first eot[b]+1 tokens of each
+ *     sequence.  Sequence b owns rows seq_off[b] .. seq_off[b+1] (seq_off: B+1 ascending int32 on the device, 1 <= length <= L = Lmax); lse keeps the
+ *     dense [B,H,L] layout.  Bucketing (optional; both pointers or neither): `order` = the B sequence ids grouped by ceil(length / 32) ascending
+ *     (DEVICE, from ocn_seq_bucket_plan), `bucket_counts` = how many sequences each group holds (HOST array of ceil(L / 32) ints summing to B).  One
+ *     launch per non-empty group, its workgroups sized for that group's length instead of L (these kernels are latency-bound: their rate is the
+ *     number of resident workgroups); results do not depend on the bucketing.
+ *   Anything else is refused before any launch.
+ * Kernels: a packed batch runs the head-resident kernels of csrc/attention.hip (one workgroup per head) and needs head_dim == 64 and L <= 320, else
+ *   OCN_ERR_UNSUPPORTED.  A dense batch runs them for head_dim 64 up to 128 tokens (forward) / 320 tokens (backward), and for everything else -- head_dim
+ *   80, 88, 96, 104, 112 or 128 (ViT-H-14, ViT-g / bigG / e), ViT-L-14's 257 tokens -- the STREAMED kernels of csrc/attention_generic.hip: 4-wave
+ *   workgroups that own four 32-row blocks and stream the operand all of them need through a two-slot LDS ring in 64-row chunks (18-35 KB of LDS per
+ *   workgroup, any sequence length).  The streamed backward needs the workspace `delta_ws`, fp32 [B*H*L] (sum_d dO*O, exchanged between its launches);
+ *   it may be NULL whenever the head-resident kernels are taken. */
+int ocn_attn_fwd(const void* qkv, void* out, float* lse, const int32_t* seq_off, const int32_t* order, const int32_t* bucket_counts, int B, int L,
+                 int H, int head_dim, int causal, float scale, ocn_stream_t stream);
+int ocn_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws, const int32_t* seq_off,
+                 const int32_t* order, const int32_t* bucket_counts, int B, int L, int H, int head_dim, int causal, float scale, ocn_stream_t stream);
 
 /* Single-query attention of a tower's LAST block, head_dim 64 (csrc/attention_pooled.hip).  Both poolers read one row per sequence of the
  * last block's output (transformer.py:829-831 `x[:, 0]`, :941-944 `x[arange, text.argmax(-1)]`), and rows only mix inside the attention: of
@@ -232,39 +228,32 @@ int ocn_embed_assemble_bwd(const float* demb, const int32_t* inv, void* dpatch_b
                            int deterministic, ocn_stream_t stream);
 
 /* ---- text tower embedding (model.py:399-401) ---------------------------------------------------
- * fwd: x[b,l,:] = table[text[b,l],:] + pos[l,:];  bwd: dtable[text[b,l],:] += dx[b,l,:] (fp32 atomics),
- * dpos[l,:] += sum_b dx[b,l,:].  text is int64. */
-int ocn_token_embed_fwd(const int64_t* text, const float* table, const float* pos, float* x, int B, int L, int C,
-                        int vocab, ocn_stream_t stream);
-int ocn_token_embed_bwd(const int64_t* text, const float* dx, float* dtable, float* dpos, int B, int L, int C, int vocab,
+ * Rows are the M = B*L tokens of a dense batch (row b*L + l carries position l) or the M rows of a packed one (see ocn_attn_fwd, ocn_seq_pack_rows).
+ * fwd: x[r,:] = table[tokens[r],:] + pos[position of r,:] (fp32 [M,C]; tokens int64 [M]).  posidx == NULL: dense, the position is r % L and
+ *   M % L == 0 is required; otherwise it is posidx[r] (int32 [M]).
+ * bwd: dtable[tokens[r],:] += dx[r,:] as a segment reduce over SORTED ids (no per-occurrence atomics): sorted_tokens = the M ids in ascending order,
+ *   order[i] = the row of dx that sorted_tokens[i] came from (torch.sort on the device).  dtable must arrive ZEROED (complete runs are stored, not
+ *   added).  dpos[l,:] += the sum of dx over the rows at position l: seq_off == NULL: dense, rows b*L + l and M == B*L is required; otherwise
+ *   rows seq_off[b] + l of the sequences longer than l.  dx is fp32 or (dx_is_bf16) bf16 [M, C], 16-byte aligned like dtable.
+ * deterministic != 0 (here and in ocn_embed_assemble_bwd): the reproducible form -- every run of equal ids is summed by ONE workgroup in sorted
+ *   order (needs a STABLE sort), dpos / dcls by a single writer per element in batch order: no fp32 atomics, bit-identical from run to run
+ *   (torch.use_deterministic_algorithms); long runs (SOT / EOT, the zero padding of a dense batch) serialise. */
+int ocn_token_embed_fwd(const int64_t* tokens, const int32_t* posidx, const float* table, const float* pos, float* x, long M, int L, int C, int vocab,
                         ocn_stream_t stream);
+int ocn_token_embed_bwd(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable, float* dpos,
+                        const int32_t* seq_off, int B, int L, long M, int C, int vocab, int deterministic, ocn_stream_t stream);
 
-/* The same backward from SORTED ids (no per-occurrence atomics): sorted_tokens = the B*L token ids in ascending order, order[i] = the flat
- * row (b*L + l) of dx that sorted_tokens[i] came from (any stable or unstable sort; torch.sort on the device).  dtable must arrive ZEROED
- * (complete runs are stored, not added); dpos is accumulated into.  dx is fp32 or (dx_is_bf16) bf16 [B*L, C].
- * deterministic != 0 (here, in ocn_embed_assemble_bwd and in the packed form below): the reproducible form -- every run of equal ids is summed
- * by ONE workgroup in sorted order (needs a STABLE sort), dpos / dcls by a single writer per element in batch order: no fp32 atomics, bit-identical
- * from run to run (torch.use_deterministic_algorithms); long runs (SOT / EOT, the zero padding of a dense batch) serialise. */
-int ocn_token_embed_bwd_sorted(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable, float* dpos,
-                               int B, int L, int C, int vocab, int deterministic, ocn_stream_t stream);
-
-/* ---- packed text batches (see ocn_attn_fwd_varlen) -----------------------------------------------
+/* ---- packed text batches (see ocn_attn_fwd) ------------------------------------------------------
  * seq_pack_plan: eot[b] = argmax(text[b,:]); seq_off = exclusive scan of (eot+1) (B+1 entries, seq_off[B] = packed row count M);
- *   last_row[b] = seq_off[b+1]-1 (the pooled row).  seq_pack_rows: tokens[seq_off[b]+l] = text[b,l], posidx[..] = l for l <= eot[b].
- * token_embed_fwd_rows: x[r,:] = table[tokens[r]] + pos[posidx[r]] (fp32 [M,C]).
- * token_embed_bwd_sorted_varlen: ocn_token_embed_bwd_sorted over the M packed rows (sorted_tokens / order index packed rows). */
+ *   last_row[b] = seq_off[b+1]-1 (the pooled row).  seq_pack_rows: tokens[seq_off[b]+l] = text[b,l], posidx[..] = l for l <= eot[b]. */
 int ocn_seq_pack_plan(const int64_t* text, int32_t* eot, int32_t* seq_off, int32_t* last_row, int B, int L, ocn_stream_t stream);
 /* *bad_count = number of ids outside [0, vocab) among text[0..n) (one workgroup, no atomics; written, not accumulated).  The embedding
  * kernels clamp such ids; nn.Embedding (src/open_clip/model.py:399) raises on them -- the host raises from this count. */
 int ocn_token_range_check(const int64_t* text, long n, int vocab, int32_t* bad_count, ocn_stream_t stream);
 /* order[0..B) = sequence ids grouped by ceil(length / 32) ascending, counts[k] = number of sequences with ceil(length / 32) == k + 1
- * (ceil(Lmax / 32) <= 16 entries, device): the buckets of ocn_attn_{fwd,bwd}_varlen.  The order inside a bucket is unspecified. */
+ * (ceil(Lmax / 32) <= 16 entries, device): the buckets of ocn_attn_fwd / ocn_attn_bwd.  The order inside a bucket is unspecified. */
 int ocn_seq_bucket_plan(const int32_t* seq_off, int32_t* order, int32_t* counts, int B, int Lmax, ocn_stream_t stream);
 int ocn_seq_pack_rows(const int64_t* text, const int32_t* seq_off, int64_t* tokens, int32_t* posidx, int B, int L, ocn_stream_t stream);
-int ocn_token_embed_fwd_rows(const int64_t* tokens, const int32_t* posidx, const float* table, const float* pos, float* x, long M, int C,
-                             int vocab, ocn_stream_t stream);
-int ocn_token_embed_bwd_sorted_varlen(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable,
-                                      float* dpos, const int32_t* seq_off, int B, int L, long M, int C, int vocab, int deterministic, ocn_stream_t stream);
 
 /* ---- pooling (transformer.py:786-787 'tok'; :941-944 'argmax') ---------------------------------
  * argmax_rows: idx[b] = first index of max(text[b,:]) (torch.argmax semantics)

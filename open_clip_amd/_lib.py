@@ -29,12 +29,8 @@ SIGNATURES = {
     "ocn_layernorm_fwd": [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p],
     "ocn_layernorm_bwd": [_p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p],
     "ocn_colsum_f32": [_p, _p, _i, _i, _i, _p],
-    "ocn_attn_fwd": [_p, _p, _p, _i, _i, _i, _i, _f, _p],
-    "ocn_attn_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
-    "ocn_attn_fwd_hd": [_p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
-    "ocn_attn_bwd_hd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
-    "ocn_attn_fwd_varlen": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
-    "ocn_attn_bwd_varlen": [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
+    "ocn_attn_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
+    "ocn_attn_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p],
     "ocn_attn_pooled_fwd": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
     "ocn_attn_pooled_bwd": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _p],
     "ocn_patchify": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p],
@@ -43,15 +39,12 @@ SIGNATURES = {
     "ocn_embed_assemble_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "ocn_patch_keep_plan": [_l, _i, _i, _i, _p, _p, _p],
     "ocn_patch_keep_inverse": [_p, _p, _i, _i, _i, _p],
-    "ocn_token_embed_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "ocn_token_embed_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "ocn_token_embed_bwd_sorted": [_p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p],
+    "ocn_token_embed_fwd": [_p, _p, _p, _p, _p, _l, _i, _i, _i, _p],
+    "ocn_token_embed_bwd": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _l, _i, _i, _i, _p],
     "ocn_seq_pack_plan": [_p, _p, _p, _p, _i, _i, _p],
     "ocn_seq_pack_rows": [_p, _p, _p, _p, _i, _i, _p],
     "ocn_token_range_check": [_p, _l, _i, _p, _p],
     "ocn_seq_bucket_plan": [_p, _p, _p, _i, _i, _p],
-    "ocn_token_embed_fwd_rows": [_p, _p, _p, _p, _p, _l, _i, _i, _p],
-    "ocn_token_embed_bwd_sorted_varlen": [_p, _p, _p, _i, _p, _p, _p, _i, _i, _l, _i, _i, _i, _p],
     "ocn_argmax_rows": [_p, _p, _i, _i, _p],
     "ocn_gather_rows": [_p, _i, _p, _p, _i, _i, _i, _p],
     "ocn_gather_rows_bf16": [_p, _p, _p, _i, _i, _i, _p],
@@ -96,7 +89,7 @@ DEBUG_SIGNATURES = {
 _SPECIAL = {"ocn_last_error": ([], ctypes.c_char_p), "ocn_version": ([], _i), "ocn_gemm_tn_det_workspace_bytes": ([_i, _i, _i], _l),
             "ocn_fused_logits_ce_workspace_floats": ([_i, _i], _l), "ocn_gemm_nt_splitk_plan": ([_i, _i, _i], _i), "ocn_layernorm_bwd_det_workspace_floats": ([_i, _i], _l), "ocn_get_tile_rescue": ([], _i)}
 
-ABI_VERSION = 108  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
+ABI_VERSION = 109  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
 
 _lib = None
 _lock = threading.Lock()

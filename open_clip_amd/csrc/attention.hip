@@ -633,23 +633,29 @@ int check_attn(const char* name, int B, int L, int H) {
 }  // namespace
 
 namespace {
+// attn_launch<kernel>::run raises the kernel's dynamic-LDS limit to the CU's 160 KiB the first time that instantiation is met, and launches it.  Instantiations
+// of one kernel template share run's type, so a launch function picks one by its conditions and spells the argument list once.
+template <auto Kernel>
+struct attn_launch;
+template <typename... P, void (*Kernel)(P...)>
+struct attn_launch<Kernel> {
+    static void run(dim3 grid, dim3 block, int lds, hipStream_t st, P... args) {
+        static const hipError_t raised = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)raised;
+        hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    }
+};
+
 // One launch of `nseq` sequences whose workgroups have `nw` waves (32 rows each).  Dense batches and un-bucketed packed batches: one
 // launch with nw = ceil(L / 32); bucketed packed batches: one launch per non-empty bucket (see seq_index).
 int attn_fwd_launch(const void* qkv, void* out, float* lse, const int32_t* seq_off, const int32_t* order, int order_off, int nseq, int nw,
                     int L, int H, int causal, float scale, hipStream_t st) {
     const int lds = 3 * nw * 32 * 128;
     const bool ntl = g_ocn_tuning[9] == 2;
-    if (nw <= 4) {
-        if (ntl) hipLaunchKernelGGL((attn_fwd_kernel<256, true>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv, (bf16*)out, lse, seq_off, L, H, causal, scale, order, order_off);
-        else hipLaunchKernelGGL((attn_fwd_kernel<256, false>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv, (bf16*)out, lse, seq_off, L, H, causal, scale, order, order_off);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<640, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_fwd_kernel<640, false>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv, (bf16*)out, lse, seq_off, L, H, causal, scale, order, order_off);
-    }
+    const auto launch = nw > 4 ? attn_launch<attn_fwd_kernel<640, false>>::run
+                        : ntl  ? attn_launch<attn_fwd_kernel<256, true>>::run
+                               : attn_launch<attn_fwd_kernel<256, false>>::run;
+    launch(dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv, (bf16*)out, lse, seq_off, L, H, causal, scale, order, order_off);
     OCN_CHECK_LAUNCH("ocn_attn_fwd");
     return OCN_OK;
 }
@@ -670,7 +676,7 @@ int attn_fwd_impl(const void* qkv, void* out, float* lse, const int32_t* seq_off
     if (int e = check_attn("ocn_attn_fwd", B, L, H)) return e;
     const int nw = ocn_cdiv(L, 32);
     if (!order) return attn_fwd_launch(qkv, out, lse, seq_off, nullptr, 0, B, nw, L, H, causal, scale, (hipStream_t)stream);
-    if (int e = check_buckets("ocn_attn_fwd_varlen", bucket_counts, B, L)) return e;
+    if (int e = check_buckets("ocn_attn_fwd", bucket_counts, B, L)) return e;
     for (int k = 1, off = 0; k <= nw; off += bucket_counts[k - 1], ++k)
         if (bucket_counts[k - 1] > 0)
             if (int e = attn_fwd_launch(qkv, out, lse, seq_off, order, off, bucket_counts[k - 1], k, L, H, causal, scale, (hipStream_t)stream)) return e;
@@ -683,14 +689,10 @@ int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const fl
     OCN_CHECK_ARG(lds <= 160 * 1024, "ocn_attn_bwd: L=%d needs %d bytes of LDS (> 160 KiB)", L, lds);
     if (g_ocn_tuning[5] > 0 && lds + g_ocn_tuning[5] * 1024 <= 160 * 1024) lds += g_ocn_tuning[5] * 1024;  // developer knob: lower the occupancy
     const int lds5 = 5 * nw * 32 * 128 + 2 * nw * 32 * 4;
+    const dim3 grid(nseq * H), block(nw * 64);
     if (causal && nw >= 2 && nw <= 3 && g_ocn_tuning[6] != 1 && g_ocn_tuning[1] == 0) {  // developer knob 6 = 1: use the generic kernel
-        static bool cattr_set = false;
-        if (!cattr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_causal_kernel<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            cattr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_causal_kernel<256, 2>), dim3(nseq * H), dim3(nw * 64), lds5, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, scale, order, order_off);
+        attn_launch<attn_bwd_causal_kernel<256, 2>>::run(grid, block, lds5, st, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv,
+                                                         seq_off, L, H, scale, order, order_off);
         OCN_CHECK_LAUNCH("ocn_attn_bwd");
         return OCN_OK;
     }
@@ -700,38 +702,14 @@ int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const fl
     // The CALL's longest sequence has at most two key blocks (the image tower's 50 tokens): delta from P and dP, O is not read.  Decided per call, not per
     // bucket: results must not depend on the bucketing, and the packed text tower (Lmax = 77) must stay bit-identical to the dense one, whose kernels
     // read O.  (developer knob 2 = 6: the O-reading form, A/B)
-    if (ocn_cdiv(L, 32) <= 2 && two_pass && g_ocn_tuning[2] != 6) {
-        hipLaunchKernelGGL((attn_bwd_kernel<256, 3, true, true>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order, order_off);
-    } else if (nw <= 4 && two_pass) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<256, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_kernel<256, 3, true>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order, order_off);
-    } else if (nw <= 4) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((attn_bwd_kernel<256, 2>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order, order_off);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<640, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<640, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_set = true;
-        }
-        // up to 10 waves per workgroup: three per SIMD, 168 registers -- the one-pass build spills 17 of them there, the two-pass one none
-        if (two_pass) hipLaunchKernelGGL((attn_bwd_kernel<640, 1, true>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order, order_off);
-        else hipLaunchKernelGGL((attn_bwd_kernel<640, 1>), dim3(nseq * H), dim3(nw * 64), lds, st, (const bf16*)qkv,
-                           (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order, order_off);
-    }
+    const bool delta_p = ocn_cdiv(L, 32) <= 2 && two_pass && g_ocn_tuning[2] != 6;
+    // beyond four waves (up to 10 per workgroup: three per SIMD, 168 registers) the one-pass build spills 17 registers, the two-pass one none
+    const auto launch = delta_p    ? attn_launch<attn_bwd_kernel<256, 3, true, true>>::run
+                        : nw <= 4  ? (two_pass ? attn_launch<attn_bwd_kernel<256, 3, true>>::run : attn_launch<attn_bwd_kernel<256, 2>>::run)
+                        : two_pass ? attn_launch<attn_bwd_kernel<640, 1, true>>::run
+                                   : attn_launch<attn_bwd_kernel<640, 1>>::run;
+    launch(grid, block, lds, st, (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, (bf16*)dqkv, seq_off, L, H, causal, scale, g_ocn_tuning[1], order,
+           order_off);
     OCN_CHECK_LAUNCH("ocn_attn_bwd");
     return OCN_OK;
 }
@@ -742,7 +720,7 @@ int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const floa
     if (int e = check_attn("ocn_attn_bwd", B, L, H)) return e;
     const int nw = ocn_cdiv(L, 32);
     if (!order) return attn_bwd_launch(qkv, out, dout, lse, dqkv, seq_off, nullptr, 0, B, nw, L, H, causal, scale, (hipStream_t)stream);
-    if (int e = check_buckets("ocn_attn_bwd_varlen", bucket_counts, B, L)) return e;
+    if (int e = check_buckets("ocn_attn_bwd", bucket_counts, B, L)) return e;
     for (int k = 1, off = 0; k <= nw; off += bucket_counts[k - 1], ++k)
         if (bucket_counts[k - 1] > 0)
             if (int e = attn_bwd_launch(qkv, out, dout, lse, dqkv, seq_off, order, off, bucket_counts[k - 1], k, L, H, causal, scale, (hipStream_t)stream)) return e;
@@ -750,40 +728,12 @@ int attn_bwd_impl(const void* qkv, const void* out, const void* dout, const floa
 }
 }  // namespace
 
-extern "C" int ocn_attn_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int causal, float scale, ocn_stream_t stream) {
-    return attn_fwd_impl(qkv, out, lse, nullptr, nullptr, nullptr, B, L, H, causal, scale, stream);
-}
-
-extern "C" int ocn_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int L, int H,
-                            int causal, float scale, ocn_stream_t stream) {
-    return attn_bwd_impl(qkv, out, dout, lse, dqkv, nullptr, nullptr, nullptr, B, L, H, causal, scale, stream);
-}
-
-// Packed ("varlen") batches, head_dim 64: sequence b owns rows seq_off[b] .. seq_off[b+1] of qkv / out / dout / dqkv
-// (1 <= length <= Lmax, seq_off = B + 1 ascending int32 on the device); lse keeps the dense [B, H, Lmax] layout.
-// Optional bucketing: `order` (device, B sequence ids grouped by ceil(len / 32) ascending, from ocn_seq_pack_plan) + `bucket_counts`
-// (HOST array of ceil(Lmax / 32) ints summing to B): one launch per non-empty bucket with workgroups sized for that bucket.
-extern "C" int ocn_attn_fwd_varlen(const void* qkv, void* out, float* lse, const int32_t* seq_off, const int32_t* order,
-                                   const int32_t* bucket_counts, int B, int Lmax, int H, int causal, float scale, ocn_stream_t stream) {
-    OCN_CHECK_ARG(seq_off, "ocn_attn_fwd_varlen: null seq_off");
-    OCN_CHECK_ARG((order == nullptr) == (bucket_counts == nullptr), "ocn_attn_fwd_varlen: order and bucket_counts go together");
-    return attn_fwd_impl(qkv, out, lse, seq_off, order, bucket_counts, B, Lmax, H, causal, scale, stream);
-}
-
-extern "C" int ocn_attn_bwd_varlen(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, const int32_t* seq_off,
-                                   const int32_t* order, const int32_t* bucket_counts, int B, int Lmax, int H, int causal, float scale,
-                                   ocn_stream_t stream) {
-    OCN_CHECK_ARG(seq_off, "ocn_attn_bwd_varlen: null seq_off");
-    OCN_CHECK_ARG((order == nullptr) == (bucket_counts == nullptr), "ocn_attn_bwd_varlen: order and bucket_counts go together");
-    return attn_bwd_impl(qkv, out, dout, lse, dqkv, seq_off, order, bucket_counts, B, Lmax, H, causal, scale, stream);
-}
-
-// ---- explicit head_dim: dispatch between the specialised (head_dim 64, head resident) and the generic kernels ---------------
+// ---- dispatch between the specialised (head_dim 64, head resident) and the generic kernels ----------------------------------
 int ocn_launch_attn_generic_fwd(const void* qkv, void* out, float* lse, int B, int L, int H, int D, int causal, float scale, hipStream_t st);
 int ocn_launch_attn_generic_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta, int B,
                                 int L, int H, int D, int causal, float scale, hipStream_t st);
 
-// head_dim 64: the head-resident kernels above (one workgroup per head) up to OCN_ATTN_RESIDENT_MAX_L tokens, the streamed kernels of
+// dense head_dim 64: the head-resident kernels above (one workgroup per head) up to OCN_ATTN_RESIDENT_MAX_L tokens, the streamed kernels of
 // attention_generic.hip beyond (at 257 tokens a resident head is 110 KB of LDS: one workgroup per CU, loads serialised in front of the
 // arithmetic); developer knob 7: 1 = always streamed, 2 = always resident (L <= 320)
 // measured at ViT-L-14's 257 tokens (profiles/r03_attention_long_sequences.txt): forward 2.13 ms streamed vs 2.49 resident, backward 6.3 vs 5.7
@@ -798,28 +748,44 @@ static bool attn_use_resident(int head_dim, int L, int max_l) {
     return g_ocn_tuning[7] == 2 || L <= max_l;
 }
 
-extern "C" int ocn_attn_fwd_hd(const void* qkv, void* out, float* lse, int B, int L, int H, int head_dim, int causal, float scale,
-                               ocn_stream_t stream) {
-    if (attn_use_resident(head_dim, L, OCN_ATTN_RESIDENT_MAX_L_FWD)) return ocn_attn_fwd(qkv, out, lse, B, L, H, causal, scale, stream);
-    OCN_CHECK_ARG(qkv && out && lse && B > 0 && L > 0 && H > 0, "ocn_attn_fwd_hd: bad arguments");
-    const int rc = ocn_launch_attn_generic_fwd(qkv, out, lse, B, L, H, head_dim, causal, scale, (hipStream_t)stream);
-    if (rc == 1) {
-        ocn_set_error("ocn_attn_fwd_hd: head_dim=%d, L=%d unsupported (head_dim in {64,80,88,96,104,112,128}; K and V of a head must fit 160 KiB of LDS)", head_dim, L);
+// the layout rules of the header, checked before any launch.  A packed batch always runs the head-resident kernels (the streamed ones know no seq_off).
+static int check_attn_layout(const char* fn, const int32_t* seq_off, const int32_t* order, const int32_t* bucket_counts, int L, int head_dim) {
+    OCN_CHECK_ARG((order == nullptr) == (bucket_counts == nullptr), "%s: order and bucket_counts go together (both or neither)", fn);
+    OCN_CHECK_ARG(seq_off || !order, "%s: order / bucket_counts bucket a packed batch, but seq_off is NULL (dense)", fn);
+    if (seq_off && (head_dim != 64 || L > 320)) {
+        ocn_set_error("%s: a packed batch (seq_off != NULL) needs head_dim == 64 and L <= 320 (head_dim=%d, L=%d)", fn, head_dim, L);
         return OCN_ERR_UNSUPPORTED;
     }
-    OCN_CHECK_LAUNCH("ocn_attn_fwd_hd");
     return OCN_OK;
 }
 
-extern "C" int ocn_attn_bwd_hd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws, int B,
-                               int L, int H, int head_dim, int causal, float scale, ocn_stream_t stream) {
-    if (attn_use_resident(head_dim, L, OCN_ATTN_RESIDENT_MAX_L_BWD)) return ocn_attn_bwd(qkv, out, dout, lse, dqkv, B, L, H, causal, scale, stream);
-    OCN_CHECK_ARG(qkv && out && dout && lse && dqkv && delta_ws && B > 0 && L > 0 && H > 0, "ocn_attn_bwd_hd: bad arguments");
-    const int rc = ocn_launch_attn_generic_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, L, H, head_dim, causal, scale, (hipStream_t)stream);
-    if (rc == 1) {
-        ocn_set_error("ocn_attn_bwd_hd: head_dim=%d, L=%d unsupported (head_dim in {64,80,88,96,104,112,128}; Q and dO of a head must fit 160 KiB of LDS)", head_dim, L);
-        return OCN_ERR_UNSUPPORTED;
-    }
-    OCN_CHECK_LAUNCH("ocn_attn_bwd_hd");
+static int attn_generic_unsupported(const char* fn, const char* operands, int head_dim, int L) {
+    ocn_set_error("%s: head_dim=%d, L=%d unsupported (head_dim in {64,80,88,96,104,112,128}; %s of a head must fit 160 KiB of LDS)", fn, head_dim, L, operands);
+    return OCN_ERR_UNSUPPORTED;
+}
+
+extern "C" int ocn_attn_fwd(const void* qkv, void* out, float* lse, const int32_t* seq_off, const int32_t* order, const int32_t* bucket_counts, int B,
+                            int L, int H, int head_dim, int causal, float scale, ocn_stream_t stream) {
+    if (int e = check_attn_layout("ocn_attn_fwd", seq_off, order, bucket_counts, L, head_dim)) return e;
+    if (seq_off || attn_use_resident(head_dim, L, OCN_ATTN_RESIDENT_MAX_L_FWD))
+        return attn_fwd_impl(qkv, out, lse, seq_off, order, bucket_counts, B, L, H, causal, scale, stream);
+    OCN_CHECK_ARG(qkv && out && lse && B > 0 && L > 0 && H > 0, "ocn_attn_fwd: bad arguments");
+    if (ocn_launch_attn_generic_fwd(qkv, out, lse, B, L, H, head_dim, causal, scale, (hipStream_t)stream) == 1)
+        return attn_generic_unsupported("ocn_attn_fwd", "K and V", head_dim, L);
+    OCN_CHECK_LAUNCH("ocn_attn_fwd");
+    return OCN_OK;
+}
+
+extern "C" int ocn_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* delta_ws, const int32_t* seq_off,
+                            const int32_t* order, const int32_t* bucket_counts, int B, int L, int H, int head_dim, int causal, float scale,
+                            ocn_stream_t stream) {
+    if (int e = check_attn_layout("ocn_attn_bwd", seq_off, order, bucket_counts, L, head_dim)) return e;
+    if (seq_off || attn_use_resident(head_dim, L, OCN_ATTN_RESIDENT_MAX_L_BWD))
+        return attn_bwd_impl(qkv, out, dout, lse, dqkv, seq_off, order, bucket_counts, B, L, H, causal, scale, stream);
+    OCN_CHECK_ARG(qkv && out && dout && lse && dqkv && B > 0 && L > 0 && H > 0, "ocn_attn_bwd: bad arguments");
+    OCN_CHECK_ARG(delta_ws, "ocn_attn_bwd: the streamed backward (head_dim=%d, L=%d) needs delta_ws", head_dim, L);
+    if (ocn_launch_attn_generic_bwd(qkv, out, dout, lse, dqkv, delta_ws, B, L, H, head_dim, causal, scale, (hipStream_t)stream) == 1)
+        return attn_generic_unsupported("ocn_attn_bwd", "Q and dO", head_dim, L);
+    OCN_CHECK_LAUNCH("ocn_attn_bwd");
     return OCN_OK;
 }

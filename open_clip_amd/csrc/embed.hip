@@ -165,49 +165,22 @@ __global__ void embed_assemble_bwd_kernel(const float* __restrict__ demb, const 
 }
 
 // ---- token embedding (model.py:399-401) ----------------------------------------------------------
-__global__ void token_embed_fwd_kernel(const int64_t* __restrict__ text, const float* __restrict__ table,
-                                       const float* __restrict__ pos, float* __restrict__ x, int B, int L, int C, int vocab) {
+// x[r] = table[tokens[r]] + pos[position of row r]: r % L in a dense batch, posidx[r] in a PACKED one (ocn_seq_pack_rows)
+template <bool PACKED>
+__global__ void token_embed_fwd_kernel(const int64_t* __restrict__ tokens, const int32_t* __restrict__ posidx, const float* __restrict__ table,
+                                       const float* __restrict__ pos, float* __restrict__ x, long M, int L, int C, int vocab) {
     const int c4n = C / 4;
-    const long total = (long)B * L * c4n;
+    const long total = M * c4n;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
         const int c = (int)(idx % c4n) * 4;
-        const long bl = idx / c4n;
-        const int l = (int)(bl % L);
-        const long tok = ocn_clamp_index(text[bl], (long)vocab);
-        *(f32x4*)(x + (size_t)bl * C + c) = *(const f32x4*)(table + (size_t)tok * C + c) + *(const f32x4*)(pos + (size_t)l * C + c);
+        const long r = idx / c4n;
+        const int l = PACKED ? posidx[r] : (int)(r % L);
+        const long tok = ocn_clamp_index(tokens[r], (long)vocab);
+        *(f32x4*)(x + (size_t)r * C + c) = *(const f32x4*)(table + (size_t)tok * C + c) + *(const f32x4*)(pos + (size_t)l * C + c);
     }
 }
 
-__global__ void token_embed_bwd_kernel(const int64_t* __restrict__ text, const float* __restrict__ dx,
-                                       float* __restrict__ dtable, float* __restrict__ dpos, int B, int L, int C, int vocab,
-                                       int bchunk) {
-    // thread <-> (position l, ONE column), loops over a chunk of the batch: a wave's atomic instruction then covers 256
-    // contiguous bytes of one table row (2 cache lines, fully used) instead of 4 bytes out of every 16 over 8 lines.
-    // Rows that share a token at the same position (SOT at l = 0, the zero padding behind EOT: about half of all
-    // tokens) are run-length combined in registers before the fp32 atomic, which removes the hot-address serialisation.
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= L * C) return;
-    const int l = idx / C, c = idx % C;
-    const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
-    float acc = 0.f, run = 0.f;
-    long run_tok = -1;
-    for (int b = b0; b < b1; ++b) {
-        const float v = dx[((size_t)b * L + l) * C + c];
-        acc += v;
-        const long tok = ocn_clamp_index(text[(size_t)b * L + l], (long)vocab);
-        if (tok != run_tok) {
-            if (run_tok >= 0) unsafeAtomicAdd(dtable + (size_t)run_tok * C + c, run);
-            run_tok = tok;
-            run = v;
-        } else {
-            run += v;
-        }
-    }
-    if (run_tok >= 0) unsafeAtomicAdd(dtable + (size_t)run_tok * C + c, run);
-    unsafeAtomicAdd(dpos + (size_t)l * C + c, acc);
-}
-
-// The same gradient from SORTED token ids (segment reduce instead of one fp32 atomic per (token, column)): `keys` = the flat token ids
+// The table gradient from SORTED token ids (segment reduce instead of one fp32 atomic per (token, column)): `keys` = the flat token ids
 // in ascending order, `order[i]` = the flat (b*L + l) row of dx that keys[i] came from.  A workgroup walks CH consecutive entries with
 // one float4 of columns per thread; a run of equal ids that starts and ends inside the chunk (and is bounded by different ids on both
 // sides) is complete and is STORED (dtable arrives zeroed), only runs that cross a chunk boundary -- the zero padding, SOT / EOT --
@@ -276,15 +249,29 @@ __global__ __launch_bounds__(128) void token_embed_bwd_sorted_kernel(const int64
     }
 }
 
-// dpos[l, :] += sum_b dx[b, l, :]   (one float4 of columns per thread, a chunk of the batch per workgroup row)
-template <typename T>
-__global__ void pos_grad_kernel(const T* __restrict__ dx, float* __restrict__ dpos, int B, int L, int C, int bchunk) {
+// dpos[l, :] += sum_b dx[b, l, :], in batch order (one float4 of columns per thread, a chunk of the batch per workgroup row).  PACKED: sequence b's
+// position l is row seq_off[b] + l, and only the sequences that HAVE a position l are summed; a chunk in which none has adds nothing.
+template <typename T, bool PACKED>
+__global__ void pos_grad_kernel(const T* __restrict__ dx, float* __restrict__ dpos, const int32_t* __restrict__ seq_off, int B, int L, int C,
+                                int bchunk) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x, c4n = C / 4;
     if (idx >= L * c4n) return;
     const int l = idx / c4n, c = (idx % c4n) * 4;
     const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int b = b0; b < b1; ++b) acc += load4f<T>(dx + ((size_t)b * L + l) * C + c);
+    bool any = !PACKED;
+    for (int b = b0; b < b1; ++b) {
+        if constexpr (PACKED) {
+            const int o = seq_off[b];
+            if (l < seq_off[b + 1] - o) {
+                acc += load4f<T>(dx + ((size_t)o + l) * C + c);
+                any = true;
+            }
+        } else {
+            acc += load4f<T>(dx + ((size_t)b * L + l) * C + c);
+        }
+    }
+    if (!any) return;
 #pragma unroll
     for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dpos + (size_t)l * C + c + e, acc[e]);
 }
@@ -338,41 +325,6 @@ __global__ void seq_pack_rows_kernel(const int64_t* __restrict__ text, const int
             posidx[o + l] = l;
         }
     }
-}
-
-__global__ void token_embed_fwd_rows_kernel(const int64_t* __restrict__ tokens, const int32_t* __restrict__ posidx,
-                                            const float* __restrict__ table, const float* __restrict__ pos, float* __restrict__ x, long M,
-                                            int C, int vocab) {
-    const int c4n = C / 4;
-    const long total = M * c4n;
-    for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
-        const int c = (int)(idx % c4n) * 4;
-        const long r = idx / c4n;
-        const long tok = ocn_clamp_index(tokens[r], (long)vocab);
-        *(f32x4*)(x + (size_t)r * C + c) = *(const f32x4*)(table + (size_t)tok * C + c) + *(const f32x4*)(pos + (size_t)posidx[r] * C + c);
-    }
-}
-
-// dpos[l, :] += sum over the sequences that HAVE a position l of dx[seq_off[b] + l, :]
-template <typename T>
-__global__ void pos_grad_varlen_kernel(const T* __restrict__ dx, float* __restrict__ dpos, const int32_t* __restrict__ seq_off, int B, int L,
-                                       int C, int bchunk) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x, c4n = C / 4;
-    if (idx >= L * c4n) return;
-    const int l = idx / c4n, c = (idx % c4n) * 4;
-    const int b0 = blockIdx.y * bchunk, b1 = min(B, b0 + bchunk);
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    bool any = false;
-    for (int b = b0; b < b1; ++b) {
-        const int o = seq_off[b];
-        if (l < seq_off[b + 1] - o) {
-            acc += load4f<T>(dx + ((size_t)o + l) * C + c);
-            any = true;
-        }
-    }
-    if (!any) return;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) unsafeAtomicAdd(dpos + (size_t)l * C + c + e, acc[e]);
 }
 
 // ---- pooling ---------------------------------------------------------------------------------------
@@ -575,44 +527,36 @@ extern "C" int ocn_embed_assemble_bwd(const float* demb, const int32_t* inv, voi
     return OCN_OK;
 }
 
-extern "C" int ocn_token_embed_fwd(const int64_t* text, const float* table, const float* pos, float* x, int B, int L, int C,
+extern "C" int ocn_token_embed_fwd(const int64_t* tokens, const int32_t* posidx, const float* table, const float* pos, float* x, long M, int L, int C,
                                    int vocab, ocn_stream_t stream) {
-    OCN_CHECK_ARG(text && table && pos && x, "ocn_token_embed_fwd: null operand");
-    OCN_CHECK_ARG(B > 0 && L > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_fwd: bad shape");
-    const long total = (long)B * L * (C / 4);
-    hipLaunchKernelGGL(token_embed_fwd_kernel, dim3(ocn_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, text, table, pos, x, B, L, C, vocab);
+    OCN_CHECK_ARG(tokens && table && pos && x, "ocn_token_embed_fwd: null operand");
+    OCN_CHECK_ARG(M > 0 && L > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_fwd: bad shape");
+    OCN_CHECK_ARG(posidx || M % L == 0, "ocn_token_embed_fwd: M=%ld is not a multiple of L=%d (dense rows carry position r %% L; a packed batch passes posidx)", M, L);
+    const auto kernel = posidx ? token_embed_fwd_kernel<true> : token_embed_fwd_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(ocn_grid_for(M * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, tokens, posidx, table, pos, x, M, L, C, vocab);
     OCN_CHECK_LAUNCH("ocn_token_embed_fwd");
     return OCN_OK;
 }
 
-extern "C" int ocn_token_embed_bwd(const int64_t* text, const float* dx, float* dtable, float* dpos, int B, int L, int C,
-                                   int vocab, ocn_stream_t stream) {
-    OCN_CHECK_ARG(text && dx && dtable && dpos, "ocn_token_embed_bwd: null operand");
-    OCN_CHECK_ARG(B > 0 && L > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_bwd: bad shape");
-    const int bchunk = 64;
-    dim3 grid(ocn_cdiv((long)L * C, 256), ocn_cdiv(B, bchunk));
-    hipLaunchKernelGGL(token_embed_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, text, dx, dtable, dpos, B, L, C, vocab, bchunk);
-    OCN_CHECK_LAUNCH("ocn_token_embed_bwd");
-    return OCN_OK;
+template <typename T>
+static void token_embed_bwd_launch(const int64_t* sorted_tokens, const int64_t* order, const T* dx, float* dtable, float* dpos, const int32_t* seq_off, int B,
+                                   int L, long M, int C, int vocab, int deterministic, hipStream_t st) {
+    const int CH = 64, bchunk = deterministic ? B : 128;  // deterministic: one batch chunk (a single writer per element of dpos) and whole runs per workgroup
+    const dim3 g1((unsigned)ocn_cdiv(M, CH)), g2(ocn_cdiv((long)L * (C / 4), 256), ocn_cdiv(B, bchunk));
+    hipLaunchKernelGGL(token_embed_bwd_sorted_kernel<T>, g1, dim3(128), 0, st, sorted_tokens, order, dx, dtable, M, C, vocab, CH, deterministic);
+    const auto pos_grad = seq_off ? pos_grad_kernel<T, true> : pos_grad_kernel<T, false>;
+    hipLaunchKernelGGL(pos_grad, g2, dim3(256), 0, st, dx, dpos, seq_off, B, L, C, bchunk);
 }
 
-extern "C" int ocn_token_embed_bwd_sorted(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable, float* dpos,
-                                          int B, int L, int C, int vocab, int deterministic, ocn_stream_t stream) {
-    OCN_CHECK_ARG(sorted_tokens && order && dx && dtable && dpos, "ocn_token_embed_bwd_sorted: null operand");
-    OCN_CHECK_ARG(B > 0 && L > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_bwd_sorted: bad shape");
-    OCN_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0, "ocn_token_embed_bwd_sorted: operands must be 16-byte aligned");
-    const long n = (long)B * L;
-    const int CH = 64, bchunk = deterministic ? B : 128;  // deterministic: one batch chunk (a single writer per element of dpos) and whole runs per workgroup
-    const dim3 g1((unsigned)ocn_cdiv(n, CH)), g2(ocn_cdiv((long)L * (C / 4), 256), ocn_cdiv(B, bchunk));
-    hipStream_t st = (hipStream_t)stream;
-    if (dx_is_bf16) {
-        hipLaunchKernelGGL(token_embed_bwd_sorted_kernel<bf16>, g1, dim3(128), 0, st, sorted_tokens, order, (const bf16*)dx, dtable, n, C, vocab, CH, deterministic);
-        hipLaunchKernelGGL(pos_grad_kernel<bf16>, g2, dim3(256), 0, st, (const bf16*)dx, dpos, B, L, C, bchunk);
-    } else {
-        hipLaunchKernelGGL(token_embed_bwd_sorted_kernel<float>, g1, dim3(128), 0, st, sorted_tokens, order, (const float*)dx, dtable, n, C, vocab, CH, deterministic);
-        hipLaunchKernelGGL(pos_grad_kernel<float>, g2, dim3(256), 0, st, (const float*)dx, dpos, B, L, C, bchunk);
-    }
-    OCN_CHECK_LAUNCH("ocn_token_embed_bwd_sorted");
+extern "C" int ocn_token_embed_bwd(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable, float* dpos,
+                                   const int32_t* seq_off, int B, int L, long M, int C, int vocab, int deterministic, ocn_stream_t stream) {
+    OCN_CHECK_ARG(sorted_tokens && order && dx && dtable && dpos, "ocn_token_embed_bwd: null operand");
+    OCN_CHECK_ARG(B > 0 && L > 0 && M > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_bwd: bad shape");
+    OCN_CHECK_ARG(seq_off || M == (long)B * L, "ocn_token_embed_bwd: M=%ld rows, but a dense batch (seq_off == NULL) has B*L = %d*%d", M, B, L);
+    OCN_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0, "ocn_token_embed_bwd: operands must be 16-byte aligned");
+    if (dx_is_bf16) token_embed_bwd_launch(sorted_tokens, order, (const bf16*)dx, dtable, dpos, seq_off, B, L, M, C, vocab, deterministic, (hipStream_t)stream);
+    else token_embed_bwd_launch(sorted_tokens, order, (const float*)dx, dtable, dpos, seq_off, B, L, M, C, vocab, deterministic, (hipStream_t)stream);
+    OCN_CHECK_LAUNCH("ocn_token_embed_bwd");
     return OCN_OK;
 }
 
@@ -688,35 +632,6 @@ extern "C" int ocn_seq_pack_rows(const int64_t* text, const int32_t* seq_off, in
     OCN_CHECK_ARG(text && seq_off && tokens && posidx && B > 0 && L > 0, "ocn_seq_pack_rows: bad arguments");
     hipLaunchKernelGGL(seq_pack_rows_kernel, dim3(ocn_grid_for((long)B * L, 256)), dim3(256), 0, (hipStream_t)stream, text, seq_off, tokens, posidx, B, L);
     OCN_CHECK_LAUNCH("ocn_seq_pack_rows");
-    return OCN_OK;
-}
-
-extern "C" int ocn_token_embed_fwd_rows(const int64_t* tokens, const int32_t* posidx, const float* table, const float* pos, float* x, long M,
-                                        int C, int vocab, ocn_stream_t stream) {
-    OCN_CHECK_ARG(tokens && posidx && table && pos && x, "ocn_token_embed_fwd_rows: null operand");
-    OCN_CHECK_ARG(M > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_fwd_rows: bad shape");
-    hipLaunchKernelGGL(token_embed_fwd_rows_kernel, dim3(ocn_grid_for(M * (C / 4), 256)), dim3(256), 0, (hipStream_t)stream, tokens, posidx, table, pos, x, M, C, vocab);
-    OCN_CHECK_LAUNCH("ocn_token_embed_fwd_rows");
-    return OCN_OK;
-}
-
-extern "C" int ocn_token_embed_bwd_sorted_varlen(const int64_t* sorted_tokens, const int64_t* order, const void* dx, int dx_is_bf16, float* dtable,
-                                                 float* dpos, const int32_t* seq_off, int B, int L, long M, int C, int vocab, int deterministic,
-                                                 ocn_stream_t stream) {
-    OCN_CHECK_ARG(sorted_tokens && order && dx && dtable && dpos && seq_off, "ocn_token_embed_bwd_sorted_varlen: null operand");
-    OCN_CHECK_ARG(B > 0 && L > 0 && M > 0 && C % 4 == 0 && vocab > 0, "ocn_token_embed_bwd_sorted_varlen: bad shape");
-    OCN_CHECK_ARG(((uintptr_t)dx & 15) == 0 && ((uintptr_t)dtable & 15) == 0, "ocn_token_embed_bwd_sorted_varlen: operands must be 16-byte aligned");
-    const int CH = 64, bchunk = deterministic ? B : 128;
-    const dim3 g1((unsigned)ocn_cdiv(M, CH)), g2(ocn_cdiv((long)L * (C / 4), 256), ocn_cdiv(B, bchunk));
-    hipStream_t st = (hipStream_t)stream;
-    if (dx_is_bf16) {
-        hipLaunchKernelGGL(token_embed_bwd_sorted_kernel<bf16>, g1, dim3(128), 0, st, sorted_tokens, order, (const bf16*)dx, dtable, M, C, vocab, CH, deterministic);
-        hipLaunchKernelGGL(pos_grad_varlen_kernel<bf16>, g2, dim3(256), 0, st, (const bf16*)dx, dpos, seq_off, B, L, C, bchunk);
-    } else {
-        hipLaunchKernelGGL(token_embed_bwd_sorted_kernel<float>, g1, dim3(128), 0, st, sorted_tokens, order, (const float*)dx, dtable, M, C, vocab, CH, deterministic);
-        hipLaunchKernelGGL(pos_grad_varlen_kernel<float>, g2, dim3(256), 0, st, (const float*)dx, dpos, seq_off, B, L, C, bchunk);
-    }
-    OCN_CHECK_LAUNCH("ocn_token_embed_bwd_sorted_varlen");
     return OCN_OK;
 }
 

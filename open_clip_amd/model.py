@@ -532,10 +532,7 @@ class _VisionEmbedFn(torch.autograd.Function):
 class _TextEmbedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, text, table, pos, pack, ex):
-        if pack is None:
-            x = ops.token_embed_fwd(text.contiguous(), table, pos)
-        else:
-            x = ops.token_embed_fwd_rows(pack.tokens, pack.posidx, table, pos)
+        x = ops.token_embed_fwd(text.contiguous() if pack is None else pack.tokens, table, pos, pack and pack.posidx)
         ctx.pack = pack
         ctx.det = ex.deterministic
         ctx.save_for_backward(text, table, pos)
@@ -545,12 +542,8 @@ class _TextEmbedFn(torch.autograd.Function):
     def backward(ctx, dx):
         text, table, pos = ctx.saved_tensors
         dtable, dpos = torch.zeros_like(table), torch.zeros_like(pos)
-        dxv = dx.contiguous()
-        if ctx.pack is None:
-            ops.token_embed_bwd_sorted(text.contiguous(), dxv, dtable, dpos, ctx.det)
-        else:
-            B, L = text.shape
-            ops.token_embed_bwd_sorted_varlen(ctx.pack.tokens, ctx.pack.seq_off, B, L, dxv, dtable, dpos, ctx.det)
+        pack = ctx.pack
+        ops.token_embed_bwd(text.contiguous() if pack is None else pack.tokens, dx.contiguous(), dtable, dpos, ctx.det, pack and pack.seq_off)
         return None, dtable, dpos, None, None
 
 

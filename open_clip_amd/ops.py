@@ -270,35 +270,27 @@ def attn_fwd(qkv, B, L, H, causal, scale, head_dim=64, seq_off=None):
     """``seq_off`` (int32 [B+1] on the device, or a SeqLayout): packed batch -- sequence b owns rows seq_off[b]..seq_off[b+1] of qkv
     (head_dim 64 only)"""
     C = H * head_dim
+    so, order, counts = (0, 0, 0)
     if seq_off is not None:
         lay = _layout(seq_off)
         if head_dim != 64 or qkv.shape[1] != 3 * C or lay.seq_off.numel() != B + 1:
             raise RuntimeError(f"attn_fwd(varlen): needs head_dim 64 and seq_off of B+1 entries (qkv {tuple(qkv.shape)}, head_dim {head_dim})")
-        out = empty((qkv.shape[0], C), BF16, qkv)
-        lse = empty((B * H * L,), F32, qkv)
         so, order, counts = lay.args(B, L)
-        _lib.call("ocn_attn_fwd_varlen", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(lse, F32, "lse"), so, order, counts,
-                  B, L, H, int(causal), float(scale), _stream())
-        return out, lse
-    if qkv.shape != (B * L, 3 * C):
+    elif qkv.shape != (B * L, 3 * C):
         raise RuntimeError(f"attn_fwd: qkv shape {tuple(qkv.shape)} != {(B * L, 3 * C)} (H={H}, head_dim={head_dim})")
-    out = empty((B * L, C), BF16, qkv)
+    out = empty((qkv.shape[0], C), BF16, qkv)
     lse = empty((B * H * L,), F32, qkv)
-    _lib.call("ocn_attn_fwd_hd", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(lse, F32, "lse"), B, L, H, head_dim, int(causal),
-              float(scale), _stream())
+    _lib.call("ocn_attn_fwd", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(lse, F32, "lse"), so, order, counts, B, L, H, head_dim,
+              int(causal), float(scale), _stream())
     return out, lse
 
 
 def attn_bwd(qkv, out, dout, lse, B, L, H, causal, scale, head_dim=64, seq_off=None):
     dqkv = empty(qkv.shape, BF16, qkv)
-    if seq_off is not None:
-        so, order, counts = _layout(seq_off).args(B, L)
-        _lib.call("ocn_attn_bwd_varlen", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"),
-                  _chk(dqkv, BF16, "dqkv"), so, order, counts, B, L, H, int(causal), float(scale), _stream())
-        return dqkv
-    delta = empty((B * H * L,), F32, qkv)  # workspace of the generic path (exchanged between its two launches)
-    _lib.call("ocn_attn_bwd_hd", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"),
-              _chk(dqkv, BF16, "dqkv"), _chk(delta, F32, "delta"), B, L, H, head_dim, int(causal), float(scale), _stream())
+    so, order, counts = _layout(seq_off).args(B, L) if seq_off is not None else (0, 0, 0)
+    delta = empty((B * H * L,), F32, qkv) if seq_off is None else None  # workspace of the streamed kernels (exchanged between their launches); dense only
+    _lib.call("ocn_attn_bwd", _chk(qkv, BF16, "qkv"), _chk(out, BF16, "out"), _chk(dout, BF16, "dout"), _chk(lse, F32, "lse"),
+              _chk(dqkv, BF16, "dqkv"), _chk(delta, F32, "delta"), so, order, counts, B, L, H, head_dim, int(causal), float(scale), _stream())
     return dqkv
 
 
@@ -416,32 +408,32 @@ def embed_assemble_bwd(demb, dpos, dcls, B, G, C, deterministic=False, inv=None,
     return dpatch
 
 
-def token_embed_fwd(text, table, pos):
-    B, L = text.shape
+def token_embed_fwd(tokens, table, pos, posidx=None):
+    """x fp32 [M, C] = table[tokens] + pos[position]: ``tokens`` is [B, L] (dense: row b*L + l carries position l) or, with ``posidx``
+    (int32 [M]), the [M] ids of a packed batch (seq_pack_rows)"""
+    if tokens.dim() != (2 if posidx is None else 1) or (posidx is not None and posidx.shape != tokens.shape):
+        raise RuntimeError(f"token_embed_fwd: tokens must be [B, L], or [M] with posidx [M] (got {tuple(tokens.shape)})")
+    M, L = tokens.numel(), (tokens.shape[1] if posidx is None else pos.shape[0])
     vocab, C = table.shape
-    x = empty((B * L, C), F32, table)
-    _lib.call("ocn_token_embed_fwd", _chk(text, torch.int64, "text"), _chk(table, F32, "table"), _chk(pos, F32, "pos"),
-              _chk(x, F32, "x"), B, L, C, vocab, _stream())
+    x = empty((M, C), F32, table)
+    _lib.call("ocn_token_embed_fwd", _chk(tokens, torch.int64, "tokens"), _chk(posidx, torch.int32, "posidx"), _chk(table, F32, "table"),
+              _chk(pos, F32, "pos"), _chk(x, F32, "x"), M, L, C, vocab, _stream())
     return x
 
 
-def token_embed_bwd(text, dx, dtable, dpos):
-    B, L = text.shape
+def token_embed_bwd(tokens, dx, dtable, dpos, deterministic=False, seq_off=None):
+    """dtable += the rows of ``dx`` by token id (``dtable`` must be zero on entry), dpos += by position.  ``tokens`` is [B, L], or the [M]
+    packed ids with ``seq_off`` (int32 [B+1]; L = the rows of ``dpos``).  The device sort of the ids is index plumbing (torch.sort); all
+    arithmetic is in ocn_token_embed_bwd."""
+    if tokens.dim() != (2 if seq_off is None else 1):
+        raise RuntimeError(f"token_embed_bwd: tokens must be [B, L], or [M] with seq_off (got {tuple(tokens.shape)})")
+    B, L = tokens.shape if seq_off is None else (seq_off.numel() - 1, dpos.shape[0])
     vocab, C = dtable.shape
-    _lib.call("ocn_token_embed_bwd", _chk(text, torch.int64, "text"), _chk(dx, F32, "dx"), _chk(dtable, F32, "dtable"),
-              _chk(dpos, F32, "dpos"), B, L, C, vocab, _stream())
-
-
-def token_embed_bwd_sorted(text, dx, dtable, dpos, deterministic=False):
-    """segment-reduce form of token_embed_bwd: ``dtable`` must be zero on entry.  The device sort of the B*L ids is index plumbing
-    (torch.sort); all arithmetic is in ocn_token_embed_bwd_sorted."""
-    B, L = text.shape
-    vocab, C = dtable.shape
-    keys, order = torch.sort(text.reshape(-1), stable=bool(deterministic))  # the reproducible form sums a run in sorted order: equal ids must keep their order
+    keys, order = torch.sort(tokens.reshape(-1), stable=bool(deterministic))  # the reproducible form sums a run in sorted order: equal ids must keep their order
     is16 = dx.dtype == BF16
-    _lib.call("ocn_token_embed_bwd_sorted", _chk(keys, torch.int64, "sorted_tokens"), _chk(order, torch.int64, "order"),
-              _chk(dx, BF16 if is16 else F32, "dx"), int(is16), _chk(dtable, F32, "dtable"), _chk(dpos, F32, "dpos"), B, L, C, vocab,
-              int(deterministic), _stream())
+    _lib.call("ocn_token_embed_bwd", _chk(keys, torch.int64, "sorted_tokens"), _chk(order, torch.int64, "order"),
+              _chk(dx, BF16 if is16 else F32, "dx"), int(is16), _chk(dtable, F32, "dtable"), _chk(dpos, F32, "dpos"),
+              _chk(seq_off, torch.int32, "seq_off"), B, L, tokens.numel(), C, vocab, int(deterministic), _stream())
 
 
 def seq_pack_plan(text, vocab=None, buckets=False):
@@ -478,26 +470,6 @@ def seq_pack_rows(text, seq_off, M):
     _lib.call("ocn_seq_pack_rows", _chk(text, torch.int64, "text"), _chk(seq_off, torch.int32, "seq_off"), _chk(tokens, torch.int64, "tokens"),
               _chk(posidx, torch.int32, "posidx"), B, L, _stream())
     return tokens, posidx
-
-
-def token_embed_fwd_rows(tokens, posidx, table, pos):
-    M = tokens.numel()
-    vocab, C = table.shape
-    x = empty((M, C), F32, table)
-    _lib.call("ocn_token_embed_fwd_rows", _chk(tokens, torch.int64, "tokens"), _chk(posidx, torch.int32, "posidx"), _chk(table, F32, "table"),
-              _chk(pos, F32, "pos"), _chk(x, F32, "x"), M, C, vocab, _stream())
-    return x
-
-
-def token_embed_bwd_sorted_varlen(tokens, seq_off, B, L, dx, dtable, dpos, deterministic=False):
-    """packed-row form of token_embed_bwd_sorted (``tokens`` = the M packed ids; ``dtable`` zero on entry)"""
-    vocab, C = dtable.shape
-    M = tokens.numel()
-    keys, order = torch.sort(tokens, stable=bool(deterministic))
-    is16 = dx.dtype == BF16
-    _lib.call("ocn_token_embed_bwd_sorted_varlen", _chk(keys, torch.int64, "sorted_tokens"), _chk(order, torch.int64, "order"),
-              _chk(dx, BF16 if is16 else F32, "dx"), int(is16), _chk(dtable, F32, "dtable"), _chk(dpos, F32, "dpos"),
-              _chk(seq_off, torch.int32, "seq_off"), B, L, M, C, vocab, int(deterministic), _stream())
 
 
 def argmax_rows(text):

@@ -53,6 +53,37 @@ def test_library_loads_and_reports_errors(lib_path):
         _lib.call("ocn_layernorm_fwd", 0, 0, 0, 0, 0, 0, 0, 0, 4, 64, 1e-5, 0)
 
 
+def test_attention_and_token_embed_layout_rules(lib_path):
+    """the dense / packed layout rules of ocn_attn_fwd / ocn_attn_bwd / ocn_token_embed_fwd / ocn_token_embed_bwd are checked on the host before any
+    launch, each refusal naming its rule.  Device operands are fake (never dereferenced); bucket_counts is a host array the library reads."""
+    import ctypes
+    from open_clip_amd import _lib
+    p, B, H = 4096, 4, 2  # a fake 16-byte aligned device pointer
+    counts = lambda L: (ctypes.c_int32 * ((L + 31) // 32))(B)
+
+    def attn(fn, seq_off, order, bucket_counts, L, head_dim, delta_ws=p):
+        operands = (p, p, p) if fn == "ocn_attn_fwd" else (p, p, p, p, p, delta_ws)  # qkv, out, lse | qkv, out, dout, lse, dqkv, delta_ws
+        _lib.call(fn, *operands, seq_off, order, bucket_counts, B, L, H, head_dim, 1, 0.125, 0)
+
+    for fn in ("ocn_attn_fwd", "ocn_attn_bwd"):
+        with pytest.raises(RuntimeError, match=fn + r" failed \(-1\): " + fn + ": order and bucket_counts go together"):
+            attn(fn, p, p, None, 77, 64)
+        with pytest.raises(RuntimeError, match=fn + r" failed \(-1\): " + fn + ": order and bucket_counts go together"):
+            attn(fn, p, None, counts(77), 77, 64)
+        with pytest.raises(RuntimeError, match=fn + r" failed \(-1\): " + fn + ": order / bucket_counts bucket a packed batch, but seq_off is NULL"):
+            attn(fn, None, p, counts(77), 77, 64)
+        with pytest.raises(RuntimeError, match=fn + r" failed \(-3\): " + fn + r": a packed batch .* needs head_dim == 64 and L <= 320 \(head_dim=80, L=77\)"):
+            attn(fn, p, None, None, 77, 80)
+        with pytest.raises(RuntimeError, match=fn + r" failed \(-3\): " + fn + r": a packed batch .* needs head_dim == 64 and L <= 320 \(head_dim=64, L=321\)"):
+            attn(fn, p, p, counts(321), 321, 64)
+    with pytest.raises(RuntimeError, match=r"ocn_attn_bwd failed \(-1\): ocn_attn_bwd: the streamed backward \(head_dim=80, L=77\) needs delta_ws"):
+        attn("ocn_attn_bwd", None, None, None, 77, 80, delta_ws=None)
+    with pytest.raises(RuntimeError, match=r"ocn_token_embed_fwd: M=100 is not a multiple of L=77 \(dense"):
+        _lib.call("ocn_token_embed_fwd", p, None, p, p, p, 100, 77, 64, 1000, 0)
+    with pytest.raises(RuntimeError, match=r"ocn_token_embed_bwd: M=100 rows, but a dense batch \(seq_off == NULL\) has B\*L = 4\*77"):
+        _lib.call("ocn_token_embed_bwd", p, p, p, 0, p, p, None, B, 77, 100, 64, 1000, 0, 0)
+
+
 def test_library_contains_gfx950_code_object(lib_path):
     data = open(lib_path, "rb").read()
     assert b"gfx950" in data

@@ -531,15 +531,11 @@ def test_text_embed_and_pool_kernels(dev):
     idx = ops.argmax_rows(text)
     assert torch.equal(idx.long(), text.argmax(-1))
     dx = torch.randn(B * L, C, generator=g).to(dev)
-    dtable, dpos = torch.zeros_like(table), torch.zeros_like(pos)
-    ops.token_embed_bwd(text, dx, dtable, dpos)
     ref = torch.zeros_like(table).index_add_(0, text.reshape(-1), dx)
-    check("token_embed_bwd dtable", dtable, ref, rel=1e-5)
-    check("token_embed_bwd dpos", dpos, dx.reshape(B, L, C).sum(0), rel=1e-5)
     dtable2, dpos2 = torch.zeros_like(table), torch.zeros_like(pos)
-    ops.token_embed_bwd_sorted(text, dx, dtable2, dpos2)
-    check("token_embed_bwd_sorted dtable", dtable2, ref, rel=1e-5)
-    check("token_embed_bwd_sorted dpos", dpos2, dx.reshape(B, L, C).sum(0), rel=1e-5)
+    ops.token_embed_bwd(text, dx, dtable2, dpos2)
+    check("token_embed_bwd dtable", dtable2, ref, rel=1e-5)
+    check("token_embed_bwd dpos", dpos2, dx.reshape(B, L, C).sum(0), rel=1e-5)
     pooled = ops.gather_rows(x, idx, B, L)
     assert torch.equal(pooled, x.reshape(B, L, C)[torch.arange(B), idx.long()])
     assert torch.equal(ops.gather_rows(x, None, B, L), x.reshape(B, L, C)[:, 0])
@@ -767,10 +763,10 @@ def test_token_embed_backward_sorted_at_bench_size(dev):
     B, L, C, V = 4096, 77, 512, 49408
     dx = torch.randn(B * L, C, device=dev, generator=torch.Generator(device=dev).manual_seed(1))
     dtable, dpos = torch.zeros(V, C, device=dev), torch.zeros(L, C, device=dev)
-    ops.token_embed_bwd_sorted(text, dx, dtable, dpos)
+    ops.token_embed_bwd(text, dx, dtable, dpos)
     ref = torch.zeros(V, C, device=dev, dtype=torch.float64).index_add_(0, text.reshape(-1), dx.double())
-    check("token_embed_bwd_sorted[4096x77x512] dtable", dtable, ref, rel=2e-6)
-    check("token_embed_bwd_sorted[4096x77x512] dpos", dpos, dx.reshape(B, L, C).double().sum(0), rel=2e-6)
+    check("token_embed_bwd[4096x77x512] dtable", dtable, ref, rel=2e-6)
+    check("token_embed_bwd[4096x77x512] dpos", dpos, dx.reshape(B, L, C).double().sum(0), rel=2e-6)
 
 
 # ---- packed ("varlen") text batches: only the first eot+1 tokens of each sequence exist (ocn_seq_pack_plan & friends) ----------------
@@ -877,18 +873,52 @@ def test_token_embed_packed(dev, B, dx_dtype):
     seq_off = plan[:B + 1]
     M = int(seq_off[-1])
     tokens, posidx = ops.seq_pack_rows(text, seq_off, M)
-    x = ops.token_embed_fwd_rows(tokens, posidx, table, pos)
+    x = ops.token_embed_fwd(tokens, table, pos, posidx)
     dense = ops.token_embed_fwd(text, table, pos).reshape(B, L, C)
     keep = torch.arange(L, device=dev)[None, :] <= eot[:, None]
     assert torch.equal(x, dense[keep])
     dx = torch.randn(M, C, device=dev, generator=torch.Generator(device=dev).manual_seed(4)).to(dx_dtype)
     dtable, dpos = torch.zeros(V, C, device=dev), torch.zeros(L, C, device=dev)
-    ops.token_embed_bwd_sorted_varlen(tokens, seq_off, B, L, dx, dtable, dpos)
+    ops.token_embed_bwd(tokens, dx, dtable, dpos, seq_off=seq_off)
     ref_t = torch.zeros(V, C, device=dev, dtype=torch.float64).index_add_(0, tokens, dx.double())
     ref_p = torch.zeros(L, C, device=dev, dtype=torch.float64).index_add_(0, posidx.long(), dx.double())
     tag = f"token_embed packed[B{B} rows {M}/{B * L} {str(dx_dtype).split('.')[-1]}]"
     check(tag + " dtable", dtable, ref_t, rel=2e-6)
     check(tag + " dpos", dpos, ref_p, rel=2e-6)
+
+
+def test_token_embed_packed_equals_dense_when_full(dev):
+    """a packed batch whose sequences all have L tokens (seq_off = multiples of L, posidx[r] = r % L) is the dense batch: the forward and the
+    reproducible backward bit for bit, the default backward against index_add_.  80 rows over 50 ids: ids repeat inside the first 64-entry chunk
+    of the sorted list (stored runs) and across its end (atomic runs)"""
+    from open_clip_amd import ops
+    B, L, C, V = 5, 16, 64, 50
+    g = torch.Generator().manual_seed(21)
+    text = torch.randint(0, V, (B, L), generator=g)
+    keys = text.reshape(-1).sort().values
+    assert keys[63] == keys[64] and bool((keys[:63].diff() == 0).any()), "the ids must exercise both branches of the sorted kernel"
+    text = text.to(dev)
+    table, pos = torch.randn(V, C, generator=g).to(dev), torch.randn(L, C, generator=g).to(dev)
+    tokens = text.reshape(-1)
+    posidx = (torch.arange(B * L, dtype=torch.int32) % L).to(dev)
+    seq_off = (torch.arange(B + 1, dtype=torch.int32) * L).to(dev)
+    assert torch.equal(ops.token_embed_fwd(tokens, table, pos, posidx), ops.token_embed_fwd(text, table, pos))
+
+    def bwd(packed, dx, det):
+        dtable, dpos = torch.zeros_like(table), torch.zeros_like(pos)
+        ops.token_embed_bwd(tokens if packed else text, dx, dtable, dpos, deterministic=det, seq_off=seq_off if packed else None)
+        return dtable, dpos
+
+    dx = torch.randn(B * L, C, generator=g).to(dev)
+    for d in (dx, dx.bfloat16()):
+        (dt_d, dp_d), (dt_p, dp_p) = bwd(False, d, True), bwd(True, d, True)
+        assert torch.equal(dt_p, dt_d) and torch.equal(dp_p, dp_d), d.dtype
+    ref_t = torch.zeros_like(table).index_add_(0, tokens, dx)
+    ref_p = torch.zeros_like(pos).index_add_(0, posidx.long(), dx)
+    for packed in (False, True):
+        dtable, dpos = bwd(packed, dx, False)
+        check(f"token_embed_bwd full layout[packed {int(packed)}] dtable", dtable, ref_t, rel=1e-5)
+        check(f"token_embed_bwd full layout[packed {int(packed)}] dpos", dpos, ref_p, rel=1e-5)
 
 
 @pytest.mark.parametrize("M", [177243, 1025])

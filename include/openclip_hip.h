@@ -65,8 +65,10 @@ const char* ocn_last_error(void);
  *   109            BREAKING: one entry point per attention / token-embedding op.  ocn_attn_fwd / ocn_attn_bwd take head_dim and a nullable seq_off, order and
  *                  bucket_counts (ocn_attn_bwd also delta_ws); ocn_token_embed_fwd takes a nullable posidx, ocn_token_embed_bwd is the sorted form with a
  *                  nullable seq_off.  Gone: ocn_attn_{fwd,bwd}_hd, ocn_attn_{fwd,bwd}_varlen, ocn_token_embed_fwd_rows, ocn_token_embed_bwd_sorted[_varlen]
- *                  and the unsorted per-occurrence-atomic ocn_token_embed_bwd. */
-#define OCN_ABI_VERSION 109
+ *                  and the unsorted per-occurrence-atomic ocn_token_embed_bwd.
+ *   110            Muon optimizer: new ocn_gemm_nt_batched, ocn_muon_momentum_multi, ocn_muon_normalize_multi, ocn_muon_apply_multi, ocn_muon_axpby
+ *                  (no signature changed). */
+#define OCN_ABI_VERSION 110
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -365,6 +367,33 @@ int ocn_adamw_multi(const void* entries, const void* chunks, int n_chunks, float
 /* chunk_ws == NULL: every chunk adds its partial sum to out[0] with an fp32 atomic (order varies from run to run).  chunk_ws = n_chunks floats:
  * the reproducible form -- every chunk stores its partial, one workgroup adds them in chunk order (clip_grad_norm_ under deterministic=True). */
 int ocn_sumsq_multi(const void* entries, const void* chunks, int n_chunks, float* out, float* chunk_ws, ocn_stream_t stream);
+
+/* ---- Muon (open_clip_amd/optim.py::NativeMuon) ---------------------------------------------------
+ * ocn_gemm_nt_batched: `batch` equal-shape problems in one launch, problem i at base + i * stride (elements):
+ *   C_i[M,N] = bf16(alpha * A_i[M,K] . B_i[N,K]^T + beta * R_i[M,N]),   Ct_i[N,M] = C_i^T when Ct != NULL.
+ * bf16 operands, fp32 accumulation, one rounding.  One workgroup per 128 x 128 tile and problem (grid = batch * tiles).  R and Ct may be NULL; C may
+ * alias R (in place), nothing else may overlap.  M, N free; K % 32 == 0; row strides of A, B, C, R and the batch strides % 8 == 0; A, B, C, R on 16 bytes. */
+int ocn_gemm_nt_batched(const void* A, int lda, int64_t strideA, const void* B, int ldb, int64_t strideB, void* C, int ldc, int64_t strideC,
+                        const void* R, int ldr, int64_t strideR, void* Ct, int ldct, int64_t strideCt, int M, int N, int K, int batch,
+                        float alpha, float beta, ocn_stream_t stream);
+/* The multi-tensor kernels of the Muon step.  `entries` = device array of 96-byte records, one per weight (a [rows, cols] fp32 matrix):
+ *   { const float* g; float* buf; float* w; bf16* w16n; bf16* w16t; bf16* xn; bf16* xt; const bf16* xfin;
+ *     int32 rows, cols, ldn, ldt, chunk0, nchunks; float step (= lr * scale), decay (= 1 - lr * weight_decay); }
+ * `chunks` = device array of int32 pairs {entry, tile}: the 64 x 64 tiles of every weight (ragged edges allowed), tile = row-major index.
+ * xn / xt: the weight-oriented and the transposed bf16 image of X in the workspace, row strides ldn >= pad32(cols), ldt >= pad32(rows), pad32(rows) resp.
+ * pad32(cols) rows; xfin: the weight-oriented image of the last iterate (row stride ldn).  gnorm_sq / max_norm: as ocn_adamw_multi.
+ *   momentum:  g = grad * clip; buf += (1 - momentum)(g - buf); u = nesterov ? g + momentum (buf - g) : buf; tile partials of sum u^2 into
+ *              chunk_ws[chunk0 + tile]; then one workgroup per entry adds its partials in a fixed order: inv_norm[i] = 1 / (||u_i|| + 1e-7)  (no atomics)
+ *   normalize: X = bf16(u * inv_norm) into xn and xt, zero in their padding
+ *   apply:     w = w * decay - step * xfin; rewrites w16n [rows, cols] and w16t [cols, rows] (rows, cols % 64 == 0) when non-NULL. */
+int ocn_muon_momentum_multi(const void* entries, int n_entries, const void* chunks, int n_chunks, float momentum, int nesterov,
+                            const float* gnorm_sq, float max_norm, float* chunk_ws, float* inv_norm, ocn_stream_t stream);
+int ocn_muon_normalize_multi(const void* entries, const void* chunks, int n_chunks, float momentum, int nesterov, const float* gnorm_sq,
+                             float max_norm, const float* inv_norm, ocn_stream_t stream);
+int ocn_muon_apply_multi(const void* entries, const void* chunks, int n_chunks, ocn_stream_t stream);
+/* out[rows, cols] = bf16(acc + beta * R) and outT[cols, rows] (nullable), all contiguous: completes a Newton-Schulz statement whose product came out
+ * of ocn_gemm_nt in fp32 (the per-matrix backend of NativeMuon) */
+int ocn_muon_axpby(const float* acc, const void* R, void* out, void* outT, int rows, int cols, float beta, ocn_stream_t stream);
 
 /* ---- collectives (loss.py:23-54 gather_features and its backward) ------------------
  * Direct RCCL calls on the caller's stream (RCCL is bound at run time from the librccl.so the process has loaded; no link-time

@@ -24,7 +24,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("get_clip_metrics", "zero_shot_accuracy", "paired_retrieval_ranks", "label_ranks"):
         from . import metrics
         return getattr(metrics, name)
-    if name in ("NativeAdamW",):
+    if name in ("NativeAdamW", "NativeMuon", "muon_param_groups"):
         from . import optim
         return getattr(optim, name)
     raise AttributeError(name)

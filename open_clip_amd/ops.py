@@ -595,6 +595,61 @@ def adamw_step(w, g, m, v, lr, beta1, beta2, eps, weight_decay, step, w_bf16=Non
               int(step), _chk(clip_coef, F32, "clip_coef"), _stream())
 
 
+# ---- Muon (optim.py::NativeMuon) ------------------------------------------------------------------------------------
+def _chk3d(t, name):
+    """bf16 [batch, rows, cols], unit inner stride, any row / batch stride -> (ptr, ld, batch stride)"""
+    if not t.is_cuda:
+        raise RuntimeError(f"open_clip_amd: '{name}' must live on the MI355X (got {t.device}); there is no CPU path")
+    if t.dtype != BF16 or t.dim() != 3 or t.stride(2) != 1:
+        raise RuntimeError(f"open_clip_amd: '{name}' must be a 3-D {BF16} stack of matrices with unit inner stride")
+    return t.data_ptr(), t.stride(1), (t.stride(0) if t.shape[0] > 1 else 0)
+
+
+def gemm_nt_batched(a, b, out, resid=None, out_t=None, alpha=1.0, beta=0.0):
+    """out[i] = bf16(alpha * a[i] @ b[i]^T + beta * resid[i]) for every i in one launch (ocn_gemm_nt_batched); a [batch, M, K], b [batch, N, K],
+    out / resid [batch, M, N], out_t [batch, N, M] (optional: the transposed result as well).  ``out`` may be ``resid`` itself."""
+    pa, lda, sa = _chk3d(a, "a")
+    pb, ldb, sb = _chk3d(b, "b")
+    po, ldc, sc = _chk3d(out, "out")
+    batch, M, K = a.shape
+    N = b.shape[1]
+    if b.shape != (batch, N, K) or out.shape != (batch, M, N) or (resid is not None and resid.shape != out.shape) or \
+            (out_t is not None and out_t.shape != (batch, N, M)):
+        raise RuntimeError(f"gemm_nt_batched: shape mismatch a{tuple(a.shape)} b{tuple(b.shape)} out{tuple(out.shape)}")
+    pr, ldr, sr = (0, 0, 0) if resid is None else _chk3d(resid, "resid")
+    pt, ldt, st = (0, 0, 0) if out_t is None else _chk3d(out_t, "out_t")
+    _lib.call("ocn_gemm_nt_batched", pa, lda, sa, pb, ldb, sb, po, ldc, sc, pr, ldr, sr, pt, ldt, st, M, N, K, batch, float(alpha), float(beta), _stream())
+    return out
+
+
+def muon_momentum_multi(entries, n_entries, chunks, n_chunks, momentum, nesterov, gnorm_sq, max_norm, chunk_ws, inv_norm):
+    """momentum buffers, update directions' tile partials and inv_norm = 1 / (||u|| + 1e-7) per matrix (ocn_muon_momentum_multi; tables as optim.py builds them)"""
+    _lib.call("ocn_muon_momentum_multi", _chk(entries, torch.uint8, "entries"), int(n_entries), _chk(chunks, torch.int32, "chunks"), int(n_chunks),
+              float(momentum), int(bool(nesterov)), _chk(gnorm_sq, F32, "gnorm_sq"), float(max_norm), _chk(chunk_ws, F32, "chunk_ws"),
+              _chk(inv_norm, F32, "inv_norm"), _stream())
+
+
+def muon_normalize_multi(entries, chunks, n_chunks, momentum, nesterov, gnorm_sq, max_norm, inv_norm):
+    """X = bf16(u * inv_norm) into the workspace images of every matrix (ocn_muon_normalize_multi)"""
+    _lib.call("ocn_muon_normalize_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), float(momentum),
+              int(bool(nesterov)), _chk(gnorm_sq, F32, "gnorm_sq"), float(max_norm), _chk(inv_norm, F32, "inv_norm"), _stream())
+
+
+def muon_apply_multi(entries, chunks, n_chunks):
+    """w = w * decay - step * X and the bf16 operand copies, for every matrix (ocn_muon_apply_multi)"""
+    _lib.call("ocn_muon_apply_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), _stream())
+
+
+def muon_axpby(acc, resid, out, out_t=None, beta=1.0):
+    """out = bf16(acc + beta * resid), out_t = out^T (optional); acc fp32 [rows, cols], the rest bf16, all contiguous (ocn_muon_axpby)"""
+    rows, cols = acc.shape
+    if resid.shape != acc.shape or out.shape != acc.shape or (out_t is not None and out_t.shape != (cols, rows)):
+        raise RuntimeError("muon_axpby: shape mismatch")
+    _lib.call("ocn_muon_axpby", _chk(acc, F32, "acc"), _chk(resid, BF16, "resid"), _chk(out, BF16, "out"), _chk(out_t, BF16, "out_t"), rows, cols,
+              float(beta), _stream())
+    return out
+
+
 # ---- validation metrics (open_clip_train/metrics.py, zero_shot.py) -------------------------------------------------
 def _on_gpu(t, dtype, name):
     """device and dtype as ``_chk``; a strided view is made contiguous here (the rank kernels take dense rows only)"""

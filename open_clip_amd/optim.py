@@ -10,7 +10,10 @@ kernel also rewrites the cached bf16 copies ([out,in] and the transposed [in,out
 kernels run in the next forward.  ``grad_clip_norm`` fuses ``torch.nn.utils.clip_grad_norm_`` (train.py:181): one
 multi-tensor sum of squares, the coefficient is applied inside the AdamW kernel (``.grad`` is left unscaled).
 ``param_groups_like_reference`` reproduces the reference's grouping rule (optim.py:67-77,178-208: 1-D params and
-``model.no_weight_decay()`` names get weight_decay 0)."""
+``model.no_weight_decay()`` names get weight_decay 0).
+
+``NativeMuon`` (below) is the second optimizer: momentum + Newton-Schulz orthogonalisation for the matrices (csrc/muon.hip), this file's AdamW tables for
+every other parameter; ``muon_param_groups`` builds the reference's fallback groups for it."""
 import numpy as np
 import torch
 
@@ -199,6 +202,306 @@ class NativeAdamW(torch.optim.Optimizer):
         params = [p for _, p in active]
         torch.autograd.graph.increment_version(params)  # raw-pointer update
         for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launch
+            for c in self.weight_caches:
+                c.mark_fresh(p, n16, t16)
+        return loss
+
+
+# ---- Muon -------------------------------------------------------------------------------------------------------------------------------
+# Momentum + Newton-Schulz orthogonalisation for the 2-D hidden weights, AdamW for everything else (csrc/muon.hip states the arithmetic).
+NS_COEFFS = (3.4445, -4.7750, 2.0315)
+ADJUST_LR = ("match_rms_adamw", "original")
+DEFAULT_FALLBACK = ("token_embedding.weight", "positional_embedding", "visual.positional_embedding", "visual.class_embedding", "logit_scale", "logit_bias")
+_MUON_ENTRY = np.dtype([("g", "<u8"), ("buf", "<u8"), ("w", "<u8"), ("w16n", "<u8"), ("w16t", "<u8"), ("xn", "<u8"), ("xt", "<u8"), ("xfin", "<u8"),
+                        ("rows", "<i4"), ("cols", "<i4"), ("ldn", "<i4"), ("ldt", "<i4"), ("chunk0", "<i4"), ("nchunks", "<i4"),
+                        ("step", "<f4"), ("decay", "<f4")])
+assert _MUON_ENTRY.itemsize == 96
+
+
+def muon_param_groups(model, weight_decay, fallback_list=DEFAULT_FALLBACK):
+    """the reference's ``wd_param_groups(model, weight_decay, exclude_fn, fallback_fn)`` (optim.py:178-208) with ``fallback_fn`` built from
+    ``--opt-fallback-list``-style patterns (optim.py:392-394: ``fnmatch.fnmatchcase`` on the full parameter name): up to four groups keyed by
+    (no weight decay, fallback), named "no_wd" / "wd" (+ "/fallback"), the matched ones flagged ``use_fallback=True``.  The no-decay rule is
+    ``param_groups_like_reference``'s (1-D parameters and ``model.no_weight_decay()`` names)."""
+    import fnmatch
+    skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
+    patterns = tuple(fallback_list or ())
+    buckets = {}
+    for n, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        n = n[len("module."):] if n.startswith("module.") else n
+        no_wd = p.ndim <= 1 or n in skip
+        fb = any(fnmatch.fnmatchcase(n, pat) for pat in patterns)
+        if (no_wd, fb) not in buckets:
+            group = {"params": [], "weight_decay": 0.0 if no_wd else weight_decay, "group_name": ("no_wd" if no_wd else "wd") + ("/fallback" if fb else "")}
+            if fb:
+                group["use_fallback"] = True
+            buckets[(no_wd, fb)] = group
+        buckets[(no_wd, fb)]["params"].append(p)
+    return list(buckets.values())
+
+
+def takes_muon(group, p):
+    """the routing rule: a parameter of a group without a truthy ``use_fallback`` takes the Muon update if it has at least two dimensions"""
+    return not group.get("use_fallback") and p.ndim >= 2
+
+
+def muon_lr_scale(adjust_lr, rows, cols):
+    if adjust_lr == "match_rms_adamw":
+        return 0.2 * max(rows, cols) ** 0.5
+    if adjust_lr == "original":
+        return max(1.0, rows / cols) ** 0.5
+    raise ValueError(f"NativeMuon: adjust_lr must be one of {ADJUST_LR} (got {adjust_lr!r})")
+
+
+def _pad32(n):
+    return (n + 31) // 32 * 32
+
+
+class _Table:
+    """a record table that travels host -> device every step through one of TWO pinned buffers used alternately (see NativeAdamW._build_plan)"""
+
+    def __init__(self, records, dev):
+        self.records = records
+        nbytes = records.size * records.dtype.itemsize
+        self.host = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.copied, self.turn = [None, None], 0
+
+    def upload(self):
+        turn, self.turn = self.turn, 1 - self.turn
+        if self.copied[turn] is not None and not self.copied[turn].query():
+            self.copied[turn].synchronize()
+        self.host[turn].numpy()[:] = self.records.view(np.uint8).reshape(-1)
+        self.dev.copy_(self.host[turn], non_blocking=True)
+        self.copied[turn] = torch.cuda.Event()
+        self.copied[turn].record()
+        return self.dev
+
+
+class NativeMuon(torch.optim.Optimizer):
+    """Muon for the matrices, AdamW for the rest, in a fixed number of launches per step.
+
+    Routing (``takes_muon``): a parameter with ``ndim >= 2`` in a group without a truthy ``use_fallback`` takes the Muon update -- a 4-D weight as
+    ``[shape[0], -1]``, ``in_proj_weight`` as one ``[3C, C]`` matrix; every other parameter takes AdamW through the tables of ``NativeAdamW``
+    (``ocn_adamw_multi``) with the group's ``lr * fallback_lr_scale``, ``betas``, ``eps`` and ``weight_decay``.  Group keys such as ``group_name`` and
+    ``lr_scale`` are carried and ignored; ``lr`` is re-read every step.  ``grad_clip_norm`` is the coefficient of the global norm over ALL parameters,
+    summed in a fixed order; ``.grad`` stays unscaled.  Nothing on the Muon path uses an fp32 atomic: a step is bit-reproducible.
+
+    The Newton-Schulz products of all equal-shape matrices run as three ``ocn_gemm_nt_batched`` launches per iteration (``_backend="batched"``);
+    ``_backend="per_matrix"`` sends one matrix at a time through ``ocn_gemm_nt`` (cross-check and timing comparison)."""
+
+    def __init__(self, params, lr=0.02, weight_decay=0.0, momentum=0.95, nesterov=True, ns_steps=5, adjust_lr="match_rms_adamw", betas=(0.9, 0.95),
+                 eps=1e-8, fallback_lr_scale=1.0, grad_clip_norm=None, weight_caches=(), _backend="batched"):
+        if adjust_lr not in ADJUST_LR:
+            raise ValueError(f"NativeMuon: adjust_lr must be one of {ADJUST_LR} (got {adjust_lr!r})")
+        if int(ns_steps) != ns_steps or ns_steps < 1:
+            raise ValueError(f"NativeMuon: ns_steps must be an integer >= 1 (got {ns_steps!r})")
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError(f"NativeMuon: momentum must lie in [0, 1) (got {momentum!r})")
+        if _backend not in ("batched", "per_matrix"):
+            raise ValueError(f"NativeMuon: unknown backend {_backend!r}")
+        super().__init__(params, dict(lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=bool(nesterov), ns_steps=int(ns_steps),
+                                      adjust_lr=adjust_lr, betas=tuple(betas), eps=eps, fallback_lr_scale=fallback_lr_scale))
+        self.grad_clip_norm = grad_clip_norm
+        self.weight_caches = list(weight_caches)
+        self._backend = _backend
+        self._plan = self._plan_key = None
+        self.last_grad_norm_sq = None  # device scalar of the most recent step when grad_clip_norm is set
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._plan = self._plan_key = None
+        for st in self.state.values():
+            if torch.is_tensor(st.get("step")):
+                st["step"] = int(st["step"].item())
+
+    def _copies_of(self, p):
+        n = t = None
+        if p.ndim in (2, 4):
+            for c in self.weight_caches:
+                n = c.peek(p, "n") if n is None else n
+                t = c.peek(p, "t") if t is None else t
+        return n, t
+
+    def _state_of(self, p, muon):
+        st = self.state[p]
+        if not st:
+            if muon:
+                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            else:
+                st["step"] = 0
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    def _build_plan(self, active, ns_steps):
+        """static part of the step: state tensors, the Newton-Schulz workspace per padded shape, chunk lists, which operand copies are rewritten"""
+        dev = active[0][1].device
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        muon = [i for i, (g, p) in enumerate(active) if takes_muon(g, p)]
+        fb = [i for i, (g, p) in enumerate(active) if not takes_muon(g, p)]
+        plan = {"muon": muon, "fb": fb, "copies": [(None, None)] * len(active)}
+        # AdamEntry records of EVERY active parameter: the squared gradient norm runs over all of them, AdamW over the fallback ones
+        ent = np.zeros(len(active), dtype=_ENTRY)
+        all_chunks, fb_chunks = [], []
+        for i, (group, p) in enumerate(active):
+            e = ent[i]
+            e["numel"], e["rows"], e["cols"] = p.numel(), 1, p.numel()
+            k = -(-p.numel() // _CHUNK)
+            c = np.empty((k, 2), dtype=np.int32)
+            c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
+            all_chunks.append(c)
+            if i in fb:
+                self._state_of(p, False)
+                n16, _ = self._copies_of(p)
+                e["w16n"] = 0 if n16 is None else n16.data_ptr()
+                plan["copies"][i] = (n16, None)  # a fallback weight's transposed copy stays on the cast path
+                fb_chunks.append(c)
+        plan["adam"] = _Table(ent, dev)
+        plan["all_chunks"], plan["n_all"] = i32(np.concatenate(all_chunks)), sum(len(c) for c in all_chunks)
+        plan["fb_chunks"], plan["n_fb"] = (i32(np.concatenate(fb_chunks)), sum(len(c) for c in fb_chunks)) if fb_chunks else (None, 0)
+        if not muon:
+            return plan
+        # Muon: matrices stacked by padded [min, max] shape; X and its transpose ping-pong between two buffers (a product reads one while it writes the other)
+        by_shape = {}
+        for j, i in enumerate(muon):
+            p = active[i][1]
+            rows, cols = p.shape[0], p.numel() // p.shape[0]
+            by_shape.setdefault((_pad32(min(rows, cols)), _pad32(max(rows, cols))), []).append(j)
+        ment = np.zeros(len(muon), dtype=_MUON_ENTRY)
+        bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
+        groups, chunks, chunk0 = [], [], 0
+        for (mp, np_), members in by_shape.items():
+            b = len(members)
+            ws = {"X": [bf(b, mp, np_), bf(b, mp, np_)], "Xt": [bf(b, np_, mp), bf(b, np_, mp)], "A": bf(b, mp, mp), "B": bf(b, mp, mp), "tall": False}
+            if self._backend == "per_matrix":
+                ws["acc_mm"] = torch.empty(mp, mp, dtype=torch.float32, device=dev)
+                ws["acc_mn"] = torch.empty(mp, np_, dtype=torch.float32, device=dev)
+            for slot, j in enumerate(members):
+                p = active[muon[j]][1]
+                self._state_of(p, True)
+                rows, cols = p.shape[0], p.numel() // p.shape[0]
+                tall = rows > cols
+                ws["tall"] = ws["tall"] or tall
+                nat, tr = (ws["Xt"], ws["X"]) if tall else (ws["X"], ws["Xt"])  # the weight-oriented image and the other one
+                n16, t16 = self._copies_of(p)
+                if t16 is not None and not (rows % 64 == 0 and cols % 64 == 0):  # odd-shaped weight: keep its transposed copy on the cast path
+                    t16 = None
+                plan["copies"][muon[j]] = (n16, t16)
+                e = ment[j]
+                e["w16n"] = 0 if n16 is None else n16.data_ptr()
+                e["w16t"] = 0 if t16 is None else t16.data_ptr()
+                e["xn"], e["xt"], e["xfin"] = nat[0][slot].data_ptr(), tr[0][slot].data_ptr(), nat[ns_steps % 2][slot].data_ptr()
+                e["rows"], e["cols"], e["ldn"], e["ldt"] = rows, cols, _pad32(cols), _pad32(rows)
+                k = -(-rows // 64) * -(-cols // 64)
+                e["chunk0"], e["nchunks"] = chunk0, k
+                chunk0 += k
+                c = np.empty((k, 2), dtype=np.int32)
+                c[:, 0], c[:, 1] = j, np.arange(k, dtype=np.int32)
+                chunks.append(c)
+            groups.append(ws)
+        plan.update(table=_Table(ment, dev), groups=groups, chunks=i32(np.concatenate(chunks)), n_chunks=chunk0,
+                    chunk_ws=torch.empty(chunk0, dtype=torch.float32, device=dev), inv_norm=torch.empty(len(muon), dtype=torch.float32, device=dev))
+        return plan
+
+    def _newton_schulz(self, ws, ns_steps):
+        a, b, c = NS_COEFFS
+        X, Xt, A, B = ws["X"], ws["Xt"], ws["A"], ws["B"]
+        for it in range(ns_steps):
+            cur, nxt = it % 2, 1 - it % 2
+            want_t = it + 1 < ns_steps or ws["tall"]  # the last iterate's transposed image is read only by tall weights (ocn_muon_apply_multi)
+            if self._backend == "batched":
+                ops.gemm_nt_batched(X[cur], X[cur], A)                                     # A = X X^T
+                ops.gemm_nt_batched(A, A, B, resid=A, alpha=c, beta=b)                     # B = b A + c A A   (A is symmetric to the bit)
+                ops.gemm_nt_batched(B, Xt[cur], X[nxt], resid=X[cur], out_t=Xt[nxt] if want_t else None, alpha=1.0, beta=a)  # X = a X + B X
+                continue
+            for i in range(A.shape[0]):
+                ops.gemm_nt(ops.EPI_BF16, X[cur][i], X[cur][i], A[i])
+                ops.gemm_nt(ops.EPI_F32, A[i], A[i], ws["acc_mm"], alpha=c)
+                ops.muon_axpby(ws["acc_mm"], A[i], B[i], None, beta=b)
+                ops.gemm_nt(ops.EPI_F32, B[i], Xt[cur][i], ws["acc_mn"])
+                ops.muon_axpby(ws["acc_mn"], X[cur][i], X[nxt][i], Xt[nxt][i] if want_t else None, beta=a)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        active = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not active:
+            return loss
+        mgroups = [g for g, p in active if takes_muon(g, p)]
+        momentum, nesterov, ns_steps = (mgroups[0]["momentum"], mgroups[0]["nesterov"], mgroups[0]["ns_steps"]) if mgroups else (0.0, False, 1)
+        key = (ns_steps,) + tuple((id(p), tuple(p.shape), takes_muon(g, p)) + tuple(map(id, self._copies_of(p))) for g, p in active)
+        if key != self._plan_key:
+            self._plan, self._plan_key = self._build_plan(active, ns_steps), key
+        plan = self._plan
+        ent = plan["adam"].records
+        grads = []
+        fb_hyper = None
+        for i, (group, p) in enumerate(active):
+            # every pointer is re-read every step (see NativeAdamW.step: load_state_dict(), model.to(), `p.data = ...` replace tensors behind an unchanged id)
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            grads.append(g)
+            if not p.is_contiguous() or g.dtype != torch.float32 or p.dtype != torch.float32:
+                raise RuntimeError("NativeMuon: parameters must be contiguous fp32 tensors with fp32 gradients")
+            e = ent[i]
+            e["w"], e["g"] = p.data_ptr(), g.data_ptr()
+            if takes_muon(group, p):
+                e["mode"] = 0 if g.data_ptr() % 16 == 0 else 2
+                continue
+            st = self._state_of(p, False)
+            st["step"] += 1
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not (m.is_contiguous() and v.is_contiguous()):
+                raise RuntimeError("NativeMuon: the AdamW moments must be contiguous")
+            if m.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32:
+                st["exp_avg"], st["exp_avg_sq"] = m, v = m.to(p.device, torch.float32), v.to(p.device, torch.float32)
+            b1, b2 = group["betas"]
+            if fb_hyper is None:
+                fb_hyper = (b1, b2, group["eps"])
+            elif fb_hyper != (b1, b2, group["eps"]):
+                raise RuntimeError("NativeMuon: all AdamW (fallback) parameters must share betas and eps")
+            e["m"], e["v"] = m.data_ptr(), v.data_ptr()
+            e["mode"] = 0 if all(t.data_ptr() % 16 == 0 for t in (p, g, m, v)) else 2
+            e["lr"], e["wd"] = group["lr"] * group["fallback_lr_scale"], group["weight_decay"]
+            e["bc1"] = 1.0 - b1 ** st["step"]
+            e["bc2_sqrt"] = (1.0 - b2 ** st["step"]) ** 0.5
+        adam_dev = plan["adam"].upload()
+        stream = torch.cuda.current_stream().cuda_stream
+        acc, gn, max_norm = None, 0, 0.0
+        if self.grad_clip_norm is not None:
+            acc = torch.zeros(1, dtype=torch.float32, device=adam_dev.device)
+            ws = torch.empty(plan["n_all"], dtype=torch.float32, device=adam_dev.device)
+            _lib.call("ocn_sumsq_multi", adam_dev.data_ptr(), plan["all_chunks"].data_ptr(), plan["n_all"], acc.data_ptr(), ws.data_ptr(), stream)
+            self.last_grad_norm_sq = acc
+            gn, max_norm = acc.data_ptr(), float(self.grad_clip_norm)
+        if plan["fb"]:
+            _lib.call("ocn_adamw_multi", adam_dev.data_ptr(), plan["fb_chunks"].data_ptr(), plan["n_fb"], float(fb_hyper[0]), float(fb_hyper[1]),
+                      float(fb_hyper[2]), gn, max_norm, stream)
+        if plan["muon"]:
+            ment = plan["table"].records
+            for j, i in enumerate(plan["muon"]):
+                group, p = active[i]
+                if (group["momentum"], group["nesterov"], group["ns_steps"]) != (momentum, nesterov, ns_steps):
+                    raise RuntimeError("NativeMuon: all Muon groups must share momentum, nesterov and ns_steps")
+                buf = self._state_of(p, True)["momentum_buffer"]
+                if buf.device != p.device or buf.dtype != torch.float32 or not buf.is_contiguous():
+                    buf = self.state[p]["momentum_buffer"] = buf.to(p.device, torch.float32).contiguous()
+                e = ment[j]
+                e["g"], e["buf"], e["w"] = grads[i].data_ptr(), buf.data_ptr(), p.data_ptr()
+                e["step"] = group["lr"] * muon_lr_scale(group["adjust_lr"], int(e["rows"]), int(e["cols"]))
+                e["decay"] = 1.0 - group["lr"] * group["weight_decay"]
+            mdev = plan["table"].upload()
+            ops.muon_momentum_multi(mdev, len(plan["muon"]), plan["chunks"], plan["n_chunks"], momentum, nesterov, acc, max_norm, plan["chunk_ws"],
+                                    plan["inv_norm"])
+            ops.muon_normalize_multi(mdev, plan["chunks"], plan["n_chunks"], momentum, nesterov, acc, max_norm, plan["inv_norm"])
+            for ws in plan["groups"]:
+                self._newton_schulz(ws, ns_steps)
+            ops.muon_apply_multi(mdev, plan["chunks"], plan["n_chunks"])
+        params = [p for _, p in active]
+        torch.autograd.graph.increment_version(params)  # raw-pointer update
+        for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launches
             for c in self.weight_caches:
                 c.mark_fresh(p, n16, t16)
         return loss

@@ -67,8 +67,9 @@ const char* ocn_last_error(void);
  *                  nullable seq_off.  Gone: ocn_attn_{fwd,bwd}_hd, ocn_attn_{fwd,bwd}_varlen, ocn_token_embed_fwd_rows, ocn_token_embed_bwd_sorted[_varlen]
  *                  and the unsorted per-occurrence-atomic ocn_token_embed_bwd.
  *   110            Muon optimizer: new ocn_gemm_nt_batched, ocn_muon_momentum_multi, ocn_muon_normalize_multi, ocn_muon_apply_multi, ocn_muon_axpby
- *                  (no signature changed). */
-#define OCN_ABI_VERSION 110
+ *                  (no signature changed).
+ *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed). */
+#define OCN_ABI_VERSION 111
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -364,6 +365,15 @@ int ocn_adamw_step(float* w, const float* g, float* m, float* v, void* w_bf16, i
  * the squared norm of every entry's gradient into out[0]. */
 int ocn_adamw_multi(const void* entries, const void* chunks, int n_chunks, float beta1, float beta2, float eps,
                     const float* gnorm_sq, float max_norm, ocn_stream_t stream);
+/* torch.optim.NAdam(decoupled_weight_decay=True) over the same tables, modes, operand copies and clip coefficient as ocn_adamw_multi (one kernel
+ * template, another element update).  The momentum schedule is host state; the record's four floats carry, in place of lr, wd, bc1, bc2_sqrt:
+ *   decay = 1 - lr * wd;  bc2 = 1 - beta2^step;  c_g = lr (1 - mu_t) / (1 - mu_product);  c_m = lr mu_next / (1 - mu_product mu_next)
+ * with mu_t = beta1 (1 - 0.5 * 0.96^(step * momentum_decay)), mu_next the same at step + 1 and mu_product the running product of mu_t.  Per element:
+ *   p *= decay;  m += (g - m) one_minus_beta1;  v = v beta2 + g g one_minus_beta2;  den = sqrt(v / bc2) + eps;  p -= c_g g / den + c_m m / den.
+ * one_minus_beta1 / one_minus_beta2 are arguments of their own: torch forms 1 - beta in double before it rounds to fp32, and the fp32 difference
+ * 1.0f - 0.98f is 1e-6 (relative) away from that, which would sit in every element of the moments.  No atomics: the update is bit-reproducible. */
+int ocn_nadamw_multi(const void* entries, const void* chunks, int n_chunks, float one_minus_beta1, float beta2, float one_minus_beta2, float eps,
+                     const float* gnorm_sq, float max_norm, ocn_stream_t stream);
 /* chunk_ws == NULL: every chunk adds its partial sum to out[0] with an fp32 atomic (order varies from run to run).  chunk_ws = n_chunks floats:
  * the reproducible form -- every chunk stores its partial, one workgroup adds them in chunk order (clip_grad_norm_ under deterministic=True). */
 int ocn_sumsq_multi(const void* entries, const void* chunks, int n_chunks, float* out, float* chunk_ws, ocn_stream_t stream);

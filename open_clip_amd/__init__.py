@@ -5,6 +5,8 @@ Public surface (mirrors the reference names):
     NativeClipLoss, NativeSigLipLoss    <- open_clip.loss.ClipLoss / SigLipLoss
     get_model_config, add_model_config  <- open_clip.factory.get_model_config / add_model_config
     create_task, create_loss            <- open_clip.factory.create_task / create_loss (the reference's task classes around the native losses)
+    create_optimizer, OptimizerCfg      <- open_clip_train.optim.create_optimizer / OptimizerCfg (the reference's parameter groups around the native
+                                           optimizers NativeAdamW, NativeNAdamW, NativeMuon: open_clip_amd.optim)
     get_clip_metrics, zero_shot_accuracy, paired_retrieval_ranks, label_ranks
                                         <- open_clip_train.metrics.get_clip_metrics / open_clip_train.zero_shot.accuracy (open_clip_amd.metrics)
 """
@@ -24,7 +26,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("get_clip_metrics", "zero_shot_accuracy", "paired_retrieval_ranks", "label_ranks"):
         from . import metrics
         return getattr(metrics, name)
-    if name in ("NativeAdamW", "NativeMuon", "muon_param_groups"):
+    if name in ("NativeAdamW", "NativeNAdamW", "NativeMuon", "muon_param_groups", "create_optimizer", "OptimizerCfg"):
         from . import optim
         return getattr(optim, name)
     raise AttributeError(name)

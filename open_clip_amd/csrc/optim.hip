@@ -96,21 +96,48 @@ struct AdamEntry {
     bf16* w16t;
     long numel;
     int rows, cols, mode, pad;
-    float lr, wd, bc1, bc2_sqrt;
+    // the four per-step floats, by update rule:  AdamW | NAdamW (nadam_one)
+    union { float lr; float decay; };      // lr                      | 1 - lr * wd
+    union { float wd; float bc2; };        // weight decay            | 1 - beta2^step
+    union { float bc1; float c_g; };       // 1 - beta1^step          | lr (1 - mu_t) / (1 - mu_product)
+    union { float bc2_sqrt; float c_m; };  // sqrt(1 - beta2^step)    | lr mu_next / (1 - mu_product mu_next)
 };
 static_assert(sizeof(AdamEntry) == 88, "AdamEntry layout is mirrored by open_clip_amd/optim.py");
 constexpr int ADAM_CHUNK = 8192;
 
-OCN_DEV float adam_one(float w, float gi, float& m, float& v, float lr, float wd, float b1, float b2, float eps, float bc1, float bc2_sqrt) {
+// omb1 / omb2: 1 - beta1 / 1 - beta2 as the entry point hands them over (ocn_adamw_multi: the fp32 differences; ocn_nadamw_multi: the caller's)
+OCN_DEV float adam_one(float w, float gi, float& m, float& v, float lr, float wd, float omb1, float b2, float omb2, float eps, float bc1, float bc2_sqrt) {
     float p = w * (1.0f - lr * wd);
-    m = m + (gi - m) * (1.0f - b1);
-    v = v * b2 + gi * gi * (1.0f - b2);
+    m = m + (gi - m) * omb1;
+    v = v * b2 + gi * gi * omb2;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     return p - (lr / bc1) * (m / denom);
 }
 
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamEntry* __restrict__ entries, const int2* __restrict__ chunks,
-                                                          float b1, float b2, float eps, const float* __restrict__ gnorm_sq, float max_norm) {
+// torch.optim.NAdam(decoupled_weight_decay=True), single-tensor form: the momentum schedule (mu_t, mu_next, mu_product) is host state, the record
+// carries what it leaves for the element:  p *= decay; m, v EMA; den = sqrt(v / bc2) + eps; p -= c_g * g / den; p -= c_m * m / den
+OCN_DEV float nadam_one(float w, float gi, float& m, float& v, float decay, float omb1, float b2, float omb2, float eps, float bc2, float c_g, float c_m) {
+    float p = w * decay;
+    m = m + (gi - m) * omb1;
+    v = v * b2 + gi * gi * omb2;
+    const float denom = sqrtf(v / bc2) + eps;
+    p -= c_g * (gi / denom);
+    return p - c_m * (m / denom);
+}
+
+enum { RULE_ADAMW = 0, RULE_NADAMW = 1 };
+
+template <int RULE>
+OCN_DEV float update_one(const AdamEntry& e, float w, float gi, float& m, float& v, float omb1, float b2, float omb2, float eps) {
+    if constexpr (RULE == RULE_NADAMW) return nadam_one(w, gi, m, v, e.decay, omb1, b2, omb2, eps, e.bc2, e.c_g, e.c_m);
+    else return adam_one(w, gi, m, v, e.lr, e.wd, omb1, b2, omb2, eps, e.bc1, e.bc2_sqrt);
+}
+
+// one walk over the chunk table for every update rule: RULE picks the element update, everything else (modes, operand copies, clip) is shared
+template <int RULE>
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __restrict__ entries, const int2* __restrict__ chunks,
+                                                         float omb1, float b2, float omb2, float eps, const float* __restrict__ gnorm_sq,
+                                                         float max_norm) {
     __shared__ float tile[64][65];
     const int2 ch = chunks[blockIdx.x];
     const AdamEntry e = entries[ch.x];
@@ -131,7 +158,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamEntry* __res
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float mj = m4[j], vj = v4[j];
-                p4[j] = adam_one(w4[j], g4[j] * gs, mj, vj, e.lr, e.wd, b1, b2, eps, e.bc1, e.bc2_sqrt);
+                p4[j] = update_one<RULE>(e, w4[j], g4[j] * gs, mj, vj, omb1, b2, omb2, eps);
                 m4[j] = mj;
                 v4[j] = vj;
             }
@@ -162,7 +189,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamEntry* __res
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float mj = m4[j], vj = v4[j];
-                p4[j] = adam_one(w4[j], g4[j] * gs, mj, vj, e.lr, e.wd, b1, b2, eps, e.bc1, e.bc2_sqrt);
+                p4[j] = update_one<RULE>(e, w4[j], g4[j] * gs, mj, vj, omb1, b2, omb2, eps);
                 m4[j] = mj;
                 v4[j] = vj;
             }
@@ -175,21 +202,21 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamEntry* __res
         if (tail + threadIdx.x < end) {
             const long i = tail + threadIdx.x;
             float mi = e.m[i], vi = e.v[i];
-            const float p = adam_one(e.w[i], e.g[i] * gs, mi, vi, e.lr, e.wd, b1, b2, eps, e.bc1, e.bc2_sqrt);
+            const float p = update_one<RULE>(e, e.w[i], e.g[i] * gs, mi, vi, omb1, b2, omb2, eps);
             e.w[i] = p; e.m[i] = mi; e.v[i] = vi;
             if (e.w16n) e.w16n[i] = f2bf(p);
         }
     } else {
         for (long i = base + threadIdx.x; i < end; i += 256) {
             float mi = e.m[i], vi = e.v[i];
-            const float p = adam_one(e.w[i], e.g[i] * gs, mi, vi, e.lr, e.wd, b1, b2, eps, e.bc1, e.bc2_sqrt);
+            const float p = update_one<RULE>(e, e.w[i], e.g[i] * gs, mi, vi, omb1, b2, omb2, eps);
             e.w[i] = p; e.m[i] = mi; e.v[i] = vi;
             if (e.w16n) e.w16n[i] = f2bf(p);
         }
     }
 }
 
-// out[0] += sum over every tensor of g^2 (same entry / chunk tables as adamw_multi_kernel)
+// out[0] += sum over every tensor of g^2 (same entry / chunk tables as adam_multi_kernel)
 // chunk_ws != nullptr: the reproducible form -- the chunk's partial is stored to its own slot, sumsq_fold_kernel adds the slots in order
 __global__ __launch_bounds__(256) void sumsq_multi_kernel(const AdamEntry* __restrict__ entries, const int2* __restrict__ chunks,
                                                           float* __restrict__ out, float* __restrict__ chunk_ws) {
@@ -287,9 +314,19 @@ extern "C" int ocn_adamw_step(float* w, const float* g, float* m, float* v, void
 extern "C" int ocn_adamw_multi(const void* entries, const void* chunks, int n_chunks, float beta1, float beta2, float eps,
                                const float* gnorm_sq, float max_norm, ocn_stream_t stream) {
     OCN_CHECK_ARG(entries && chunks && n_chunks > 0, "ocn_adamw_multi: bad arguments");
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)entries,
-                       (const int2*)chunks, beta1, beta2, eps, gnorm_sq, max_norm);
+    hipLaunchKernelGGL(adam_multi_kernel<RULE_ADAMW>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)entries,
+                       (const int2*)chunks, 1.0f - beta1, beta2, 1.0f - beta2, eps, gnorm_sq, max_norm);
     OCN_CHECK_LAUNCH("ocn_adamw_multi");
+    return OCN_OK;
+}
+
+extern "C" int ocn_nadamw_multi(const void* entries, const void* chunks, int n_chunks, float one_minus_beta1, float beta2, float one_minus_beta2,
+                                float eps, const float* gnorm_sq, float max_norm, ocn_stream_t stream) {
+    OCN_CHECK_ARG(entries && chunks, "ocn_nadamw_multi: null entry / chunk table");
+    OCN_CHECK_ARG(n_chunks > 0, "ocn_nadamw_multi: n_chunks must be positive");
+    hipLaunchKernelGGL(adam_multi_kernel<RULE_NADAMW>, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const AdamEntry*)entries,
+                       (const int2*)chunks, one_minus_beta1, beta2, one_minus_beta2, eps, gnorm_sq, max_norm);
+    OCN_CHECK_LAUNCH("ocn_nadamw_multi");
     return OCN_OK;
 }
 

@@ -1,5 +1,5 @@
-"""AdamW on the HIP path: the optimizer step of ``train.py:181-182`` -- gradient clipping,
-AdamW and the refresh of the bf16 GEMM-operand copies of the weights -- as ONE launch over the whole model.
+"""The optimizers of the HIP path: the optimizer step of ``train.py:181-182`` -- gradient clipping, the update and the refresh
+of the bf16 GEMM-operand copies of the weights -- as ONE launch over the whole model, and the reference's ``create_optimizer`` seam in front of them.
 
 ``NativeAdamW`` is a ``torch.optim.Optimizer`` with torch.optim.AdamW's semantics (decoupled weight decay, bias
 correction; verified against it in tests/test_kernels_gpu.py).  Every step it describes the parameters to the device
@@ -9,11 +9,21 @@ does not -- and launches one kernel.  When the model's ``_WeightCache`` objects 
 kernel also rewrites the cached bf16 copies ([out,in] and the transposed [in,out]) in the same pass, so no cast
 kernels run in the next forward.  ``grad_clip_norm`` fuses ``torch.nn.utils.clip_grad_norm_`` (train.py:181): one
 multi-tensor sum of squares, the coefficient is applied inside the AdamW kernel (``.grad`` is left unscaled).
-``param_groups_like_reference`` reproduces the reference's grouping rule (optim.py:67-77,178-208: 1-D params and
-``model.no_weight_decay()`` names get weight_decay 0).
 
-``NativeMuon`` (below) is the second optimizer: momentum + Newton-Schulz orthogonalisation for the matrices (csrc/muon.hip), this file's AdamW tables for
-every other parameter; ``muon_param_groups`` builds the reference's fallback groups for it."""
+``NativeNAdamW`` is the reference's second built-in optimizer (optim.py:449-453: ``torch.optim.NAdam(decoupled_weight_decay=True)``) over the same
+tables and the same kernel walk with another element update (``ocn_nadamw_multi``); ``nadam_schedule`` is its host-side momentum schedule.
+
+``NativeMuon`` (below) is the third optimizer: momentum + Newton-Schulz orthogonalisation for the matrices (csrc/muon.hip), this file's AdamW tables for
+every other parameter.
+
+``create_optimizer(model, cfg)`` / ``OptimizerCfg`` mirror ``open_clip_train.optim.create_optimizer`` (optim.py:336-472) for a ``NativeCLIP``: the
+reference's parameter groups -- ``make_wd_exclude`` (1-D parameters, ``no_weight_decay()`` names, ``--wd-exclude`` patterns), ``wd_param_groups``
+(two / four buckets) and ``layer_decay_param_groups`` (layer-wise LR decay over the towers' ``layer_groups()``) -- restated here, then the native
+optimizer that ``cfg.opt`` names.  ``param_groups_like_reference`` and ``muon_param_groups`` are the two fixed-shape callers of those builders."""
+import fnmatch
+from dataclasses import dataclass, field
+from typing import List, Optional
+
 import numpy as np
 import torch
 
@@ -22,19 +32,105 @@ from . import _lib, ops
 _ENTRY = np.dtype([("w", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("w16n", "<u8"), ("w16t", "<u8"), ("numel", "<i8"),
                    ("rows", "<i4"), ("cols", "<i4"), ("mode", "<i4"), ("pad", "<i4"),
                    ("lr", "<f4"), ("wd", "<f4"), ("bc1", "<f4"), ("bc2_sqrt", "<f4")])
-assert _ENTRY.itemsize == 88
+# the same record as ocn_nadamw_multi reads it: the four floats under NAdamW's names (the unions of AdamEntry, csrc/optim.hip)
+_NADAM_ENTRY = np.dtype(_ENTRY.descr[:-4] + [("decay", "<f4"), ("bc2", "<f4"), ("c_g", "<f4"), ("c_m", "<f4")])
+assert _ENTRY.itemsize == _NADAM_ENTRY.itemsize == 88
 _CHUNK = 8192
+DEFAULT_FALLBACK = ("token_embedding.weight", "positional_embedding", "visual.positional_embedding", "visual.class_embedding", "logit_scale", "logit_bias")
+
+
+# ---- parameter groups (open_clip_train/optim.py:67-323) -----------------------------------------------------------------------------------
+def unwrap_model(model):
+    """the module behind DDP's ``.module`` and torch.compile's ``._orig_mod``, in any nesting: parameter names and tower discovery need the real one"""
+    while True:
+        inner = getattr(model, "_orig_mod", None)
+        inner = getattr(model, "module", None) if inner is None else inner
+        if inner is None:
+            return model
+        model = inner
+
+
+def make_wd_exclude(model, extra_patterns=None):
+    """``(name, param) -> bool``: does the parameter skip weight decay (optim.py:136-157)?  Yes for every parameter with at most one dimension, for
+    the names any submodule declares through ``no_weight_decay()`` (taken relative to that submodule's path) and for full names that match one of
+    ``extra_patterns`` (``--wd-exclude``; ``fnmatch.fnmatchcase``, so ``*`` spans dots)."""
+    declared = set()
+    for path, module in model.named_modules():
+        names = getattr(module, "no_weight_decay", None)
+        if callable(names):
+            declared |= {(path + "." if path else "") + n for n in names()}
+    patterns = tuple(extra_patterns or ())
+    return lambda name, p: p.ndim <= 1 or name in declared or any(fnmatch.fnmatchcase(name, pat) for pat in patterns)
+
+
+def make_fallback_fn(fallback_list):
+    """``name -> bool`` from ``--opt-fallback-list``-style patterns (optim.py:392-394), or None for an empty list"""
+    patterns = tuple(fallback_list or ())
+    return (lambda name: any(fnmatch.fnmatchcase(name, pat) for pat in patterns)) if patterns else None
+
+
+def _bucket_groups(model, weight_decay, exclude_fn, fallback_fn, scales):
+    """the trainable parameters in ``named_parameters()`` order, bucketed by (lr_scale, no weight decay, fallback); ``scales``: None (no layer decay:
+    the groups carry no ``lr_scale``) or ``{id(param): lr_scale}`` with 1.0 for whatever it does not list"""
+    exclude_fn = exclude_fn or make_wd_exclude(model)
+    buckets = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        no_wd, fb = bool(exclude_fn(name, p)), bool(fallback_fn(name)) if fallback_fn else False
+        scale = None if scales is None else scales.get(id(p), 1.0)
+        key = (None if scale is None else round(scale, 8), no_wd, fb)
+        if key not in buckets:
+            group = {"params": [], "weight_decay": 0.0 if no_wd else weight_decay}
+            label = ("no_wd" if no_wd else "wd") + ("/fallback" if fb else "")
+            if scale is not None:
+                group["lr_scale"], label = scale, f"lr_scale={scale:.4g}/{label}"
+            group["group_name"] = label
+            if fb:
+                group["use_fallback"] = True
+            buckets[key] = group
+        buckets[key]["params"].append(p)
+    return list(buckets.values())
+
+
+def wd_param_groups(model, weight_decay, exclude_fn=None, fallback_fn=None):
+    """optim.py:178-208: "no_wd" / "wd" in order of first appearance; with ``fallback_fn`` each splits again into a "/fallback" twin flagged
+    ``use_fallback=True`` (the parameters a hybrid optimizer hands to its AdamW side)"""
+    return _bucket_groups(model, weight_decay, exclude_fn, fallback_fn, None)
+
+
+def layer_decay_param_groups(model, weight_decay, text_layer_decay=None, image_layer_decay=None, pooler_in_head=True, exclude_fn=None,
+                             fallback_fn=None):
+    """optim.py:247-323: layer-wise LR decay.  A tower with a decay gives group ``idx`` of its ``n`` ordered layer groups (``text_layer_groups`` /
+    ``visual.layer_groups``: embeddings, blocks, projection) ``lr_scale = decay ** (n - 1 - idx)``; every other parameter keeps 1.0.  Inside each
+    scale the weight-decay (and fallback) split holds; groups are named "lr_scale=<scale:.4g>/<wd|no_wd>[/fallback]" and sorted head first
+    (``-lr_scale``, then name).  The scheduler multiplies a group's LR by its ``lr_scale`` (scheduler.py:6-15)."""
+    scales = {}
+    for decay, groups in ((text_layer_decay, model.text_layer_groups), (image_layer_decay, model.visual.layer_groups)):
+        if not decay:
+            continue
+        groups = groups(pooler_in_head)
+        for idx, (_, members) in enumerate(groups):
+            for member in members:
+                for p in ([member] if isinstance(member, torch.nn.Parameter) else member.parameters()):
+                    scales[id(p)] = decay ** (len(groups) - 1 - idx)
+    return sorted(_bucket_groups(model, weight_decay, exclude_fn, fallback_fn, scales), key=lambda g: (-g["lr_scale"], g["group_name"]))
 
 
 def param_groups_like_reference(model, weight_decay=0.2):
-    skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
-    decay, no_decay = [], []
-    for n, p in model.named_parameters():
-        if not p.requires_grad:
-            continue
-        n = n[len("module."):] if n.startswith("module.") else n
-        (no_decay if (p.ndim <= 1 or n in skip) else decay).append(p)  # optim.py:67-77 exclude_from_wd + no_weight_decay()
-    return [{"params": no_decay, "weight_decay": 0.0}, {"params": decay, "weight_decay": weight_decay}]
+    """the reference's default split (optim.py:67-77,178-208) in a fixed shape: [no weight decay, weight decay], either possibly empty"""
+    model = unwrap_model(model)
+    by_name = {g["group_name"]: g["params"] for g in wd_param_groups(model, weight_decay)}
+    return [{"params": by_name.get("no_wd", []), "weight_decay": 0.0}, {"params": by_name.get("wd", []), "weight_decay": weight_decay}]
+
+
+def muon_param_groups(model, weight_decay, fallback_list=DEFAULT_FALLBACK):
+    """the reference's ``wd_param_groups(model, weight_decay, exclude_fn, fallback_fn)`` (optim.py:178-208) with ``fallback_fn`` built from
+    ``--opt-fallback-list``-style patterns (optim.py:392-394: ``fnmatch.fnmatchcase`` on the full parameter name): up to four groups keyed by
+    (no weight decay, fallback), named "no_wd" / "wd" (+ "/fallback"), the matched ones flagged ``use_fallback=True``.  The no-decay rule is
+    ``param_groups_like_reference``'s (1-D parameters and ``no_weight_decay()`` names)."""
+    model = unwrap_model(model)
+    return wd_param_groups(model, weight_decay, None, make_fallback_fn(fallback_list))
 
 
 def weight_caches_of(model):
@@ -43,19 +139,178 @@ def weight_caches_of(model):
     return [c for c in (getattr(m, "_cache", None), getattr(getattr(m, "visual", None), "_cache", None)) if c is not None]
 
 
-class NativeAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, grad_clip_norm=None, weight_caches=(),
-                 fused=True, deterministic=False):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+# ---- AdamW / NAdamW: one launch over the whole model --------------------------------------------------------------------------------------
+class _Table:
+    """a record table that travels host -> device every step through one of TWO pinned buffers used alternately: the buffer a step fills was last
+    read by the upload of two steps ago, so the wait never blocks a host that runs a step ahead of the device"""
+
+    def __init__(self, records, dev):
+        self.records = records
+        nbytes = records.size * records.dtype.itemsize
+        self.host = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.copied, self.turn = [None, None], 0
+
+    def upload(self):
+        turn, self.turn = self.turn, 1 - self.turn
+        if self.copied[turn] is not None and not self.copied[turn].query():
+            self.copied[turn].synchronize()  # the upload of two steps ago out of this pinned buffer (in practice long finished)
+        self.host[turn].numpy()[:] = self.records.view(np.uint8).reshape(-1)
+        self.dev.copy_(self.host[turn], non_blocking=True)
+        self.copied[turn] = torch.cuda.Event()
+        self.copied[turn].record()
+        return self.dev
+
+
+class _TableAdam(torch.optim.Optimizer):
+    """what NativeAdamW and NativeNAdamW share: the per-parameter state, the plan (records, modes, chunk list, operand copies), the pinned upload, the
+    fused clip and the launch.  A subclass names its entry point (``_KERNEL``), its record dtype (``_RECORD``), its scalar state (``_SCALARS``: key ->
+    (zero, type)), the group values every group must agree on because they are kernel arguments (``_shared_of``: (beta1, beta2, eps, ...)), and fills
+    the four per-step floats of a record (``_fill``)."""
+    _KERNEL = _WHO = _RECORD = None
+    _SCALARS = {"step": (0, int)}
+    _SHARED_TEXT = "betas and eps"
+
+    def _setup(self, grad_clip_norm, weight_caches, deterministic):
         self.grad_clip_norm = grad_clip_norm
         # the squared gradient norm of ``grad_clip_norm`` summed in a fixed order (per-chunk partials folded by one workgroup) instead of with
         # fp32 atomics: the optimizer's share of NativeCLIP(deterministic=True) -- the clipped update is then bit-reproducible too
         self.deterministic = bool(deterministic)
         self.weight_caches = list(weight_caches)
-        self.fused = fused
         self._plan_key = None
         self._plan = None
         self.last_grad_norm_sq = None  # device scalar of the most recent step when grad_clip_norm is set
+
+    def _shared_of(self, group):
+        b1, b2 = group["betas"]
+        return float(b1), float(b2), float(group["eps"])
+
+    def _fill(self, e, group, st, shared):
+        raise NotImplementedError
+
+    def _kernel_scalars(self, shared):
+        """the entry point's float arguments between ``n_chunks`` and ``gnorm_sq``"""
+        return shared[:3]
+
+    def _state_of(self, p):
+        st = self.state[p]
+        if not st:
+            for k, (zero, _) in self._SCALARS.items():
+                st[k] = zero
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        return st
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._plan = self._plan_key = None  # the moments are new tensors: rebuild the device table on the next step
+        for st in self.state.values():      # torch stores its scalar state (`step`, NAdam's `mu_product`) as 0-d tensors in its own checkpoints: accept both
+            for k, (_, kind) in self._SCALARS.items():
+                if torch.is_tensor(st.get(k)):
+                    st[k] = kind(st[k].item())
+
+    def _copies_of(self, p):
+        n = t = None
+        for c in self.weight_caches:
+            n = c.peek(p, "n") if n is None else n
+            t = c.peek(p, "t") if t is None else t
+        return n, t
+
+    def _build_plan(self, active):
+        """static part of the step: state tensors, operand copies, modes, chunk list (rebuilt when the set of tensors with
+        a gradient, or the set of cached operand copies, changes)"""
+        dev = active[0][1].device
+        ent = np.zeros(len(active), dtype=self._RECORD)
+        chunks, copies = [], []
+        for i, (group, p) in enumerate(active):
+            st = self._state_of(p)
+            n16, t16 = (None, None) if p.ndim != 2 and not (p.ndim == 4) else self._copies_of(p)
+            rows = p.shape[0] if p.ndim >= 2 else 1
+            cols = p.numel() // rows
+            e = ent[i]
+            e["w"], e["m"], e["v"] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+            e["w16n"] = 0 if n16 is None else n16.data_ptr()
+            e["w16t"] = 0 if t16 is None else t16.data_ptr()
+            e["numel"], e["rows"], e["cols"] = p.numel(), rows, cols
+            tile = t16 is not None and rows % 64 == 0 and cols % 64 == 0
+            if t16 is not None and not tile:  # odd-shaped weight: keep its transposed copy on the cast path
+                e["w16t"] = 0
+                t16 = None
+            e["mode"] = 1 if tile else (0 if p.data_ptr() % 16 == 0 else 2)
+            k = (rows // 64) * (cols // 64) if tile else -(-p.numel() // _CHUNK)
+            c = np.empty((k, 2), dtype=np.int32)
+            c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
+            chunks.append(c)
+            copies.append((n16, t16))
+        chunks = np.concatenate(chunks, axis=0)
+        return {"table": _Table(ent, dev), "n_chunks": int(chunks.shape[0]), "copies": copies, "chunks_dev": torch.from_numpy(chunks).to(dev)}
+
+    @torch.no_grad()
+    def _step_tables(self):
+        active = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
+        if not active:
+            return
+        key = tuple((id(p), tuple(p.shape)) + (tuple(map(id, self._copies_of(p))) if p.ndim in (2, 4) else ()) for _, p in active)
+        if key != self._plan_key:
+            self._plan, self._plan_key = self._build_plan(active), key
+        plan = self._plan
+        ent = plan["table"].records
+        shared = self._shared_of(active[0][0])
+        grads, checked = [], None
+        for i, (group, p) in enumerate(active):
+            if group is not checked:
+                if self._shared_of(group) != shared:
+                    raise RuntimeError(f"{self._WHO}: all param groups must share {self._SHARED_TEXT}")
+                checked = group
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            grads.append(g)
+            st = self._state_of(p)
+            st["step"] += 1
+            e = ent[i]
+            # every pointer of the record is re-read every step: load_state_dict(), model.to(), `p.data = ...` replace the
+            # parameter / moment tensors behind an unchanged id(p), and a cached address would then update freed memory
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if not (m.is_contiguous() and v.is_contiguous() and p.is_contiguous()):
+                raise RuntimeError(f"{self._WHO}: parameters and their moments must be contiguous")
+            if m.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32:
+                st["exp_avg"], st["exp_avg_sq"] = m, v = m.to(p.device, torch.float32), v.to(p.device, torch.float32)
+            e["w"], e["m"], e["v"], e["g"] = p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr()
+            if e["mode"] != 1:
+                e["mode"] = 0 if (p.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0) else 2
+            self._fill(e, group, st, shared)
+        entries_dev = plan["table"].upload()
+        stream = torch.cuda.current_stream().cuda_stream
+        gn, max_norm = 0, 0.0
+        if self.grad_clip_norm is not None:
+            acc = torch.zeros(1, dtype=torch.float32, device=entries_dev.device)
+            ws = torch.empty(plan["n_chunks"], dtype=torch.float32, device=acc.device) if self.deterministic else None
+            _lib.call("ocn_sumsq_multi", entries_dev.data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], acc.data_ptr(),
+                      0 if ws is None else ws.data_ptr(), stream)
+            self.last_grad_norm_sq = acc
+            gn, max_norm = acc.data_ptr(), float(self.grad_clip_norm)
+        _lib.call(self._KERNEL, entries_dev.data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], *self._kernel_scalars(shared), gn, max_norm,
+                  stream)
+        params = [p for _, p in active]
+        torch.autograd.graph.increment_version(params)  # raw-pointer update
+        for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launch
+            for c in self.weight_caches:
+                c.mark_fresh(p, n16, t16)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        self._step_tables()
+        return loss
+
+
+class NativeAdamW(_TableAdam):
+    _KERNEL, _WHO, _RECORD = "ocn_adamw_multi", "NativeAdamW (fused)", _ENTRY
+
+    def __init__(self, params, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, grad_clip_norm=None, weight_caches=(),
+                 fused=True, deterministic=False):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self._setup(grad_clip_norm, weight_caches, deterministic)
+        self.fused = fused
 
     # ---- per-tensor reference path (one ocn_adamw_step launch per tensor) ------------------------------------------
     @torch.no_grad()
@@ -83,163 +338,80 @@ class NativeAdamW(torch.optim.Optimizer):
                                group["eps"], group["weight_decay"], st["step"], clip_coef=coef)
                 torch.autograd.graph.increment_version(p)  # raw-pointer update: let the bf16 weight cache see it
 
-    def _state_of(self, p):
-        st = self.state[p]
-        if not st:
-            st["step"] = 0
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st
-
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._plan = self._plan_key = None  # the moments are new tensors: rebuild the device table on the next step
-        for st in self.state.values():      # torch stores `step` as a tensor in its own AdamW checkpoints: accept both
-            if torch.is_tensor(st.get("step")):
-                st["step"] = int(st["step"].item())
-
     # ---- fused path ---------------------------------------------------------------------------------------------------
-    def _copies_of(self, p):
-        n = t = None
-        for c in self.weight_caches:
-            n = c.peek(p, "n") if n is None else n
-            t = c.peek(p, "t") if t is None else t
-        return n, t
-
-    def _build_plan(self, active):
-        """static part of the step: state tensors, operand copies, modes, chunk list (rebuilt when the set of tensors with
-        a gradient, or the set of cached operand copies, changes)"""
-        dev = active[0][1].device
-        ent = np.zeros(len(active), dtype=_ENTRY)
-        chunks, copies = [], []
-        for i, (group, p) in enumerate(active):
-            st = self._state_of(p)
-            n16, t16 = (None, None) if p.ndim != 2 and not (p.ndim == 4) else self._copies_of(p)
-            rows = p.shape[0] if p.ndim >= 2 else 1
-            cols = p.numel() // rows
-            e = ent[i]
-            e["w"], e["m"], e["v"] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-            e["w16n"] = 0 if n16 is None else n16.data_ptr()
-            e["w16t"] = 0 if t16 is None else t16.data_ptr()
-            e["numel"], e["rows"], e["cols"] = p.numel(), rows, cols
-            tile = t16 is not None and rows % 64 == 0 and cols % 64 == 0
-            if t16 is not None and not tile:  # odd-shaped weight: keep its transposed copy on the cast path
-                e["w16t"] = 0
-                t16 = None
-            e["mode"] = 1 if tile else (0 if p.data_ptr() % 16 == 0 else 2)
-            k = (rows // 64) * (cols // 64) if tile else -(-p.numel() // _CHUNK)
-            c = np.empty((k, 2), dtype=np.int32)
-            c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
-            chunks.append(c)
-            copies.append((n16, t16))
-        chunks = np.concatenate(chunks, axis=0)
-        # the record table travels host -> device every step through one of TWO pinned buffers used alternately: the buffer a step fills
-        # was last read by the upload of two steps ago, so the wait below never blocks a host that runs a step ahead of the device
-        plan = {"entries": ent, "n_chunks": int(chunks.shape[0]), "copies": copies, "copied": [None, None], "turn": 0,
-                "chunks_dev": torch.from_numpy(chunks).to(dev),
-                "entries_host": [torch.empty(len(active) * _ENTRY.itemsize, dtype=torch.uint8).pin_memory() for _ in range(2)],
-                "entries_dev": torch.empty(len(active) * _ENTRY.itemsize, dtype=torch.uint8, device=dev)}
-        return plan
+    def _fill(self, e, group, st, shared):
+        e["lr"], e["wd"] = group["lr"], group["weight_decay"]
+        e["bc1"] = 1.0 - shared[0] ** st["step"]
+        e["bc2_sqrt"] = (1.0 - shared[1] ** st["step"]) ** 0.5
 
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        if not self.fused:
+        if self.fused:
+            self._step_tables()
+        else:
             self._step_per_tensor()
-            return loss
-        active = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
-        if not active:
-            return loss
-        key = tuple((id(p), tuple(p.shape)) + (tuple(map(id, self._copies_of(p))) if p.ndim in (2, 4) else ()) for _, p in active)
-        if key != self._plan_key:
-            self._plan, self._plan_key = self._build_plan(active), key
-        plan = self._plan
-        turn = plan["turn"]
-        plan["turn"] = 1 - turn
-        if plan["copied"][turn] is not None and not plan["copied"][turn].query():
-            plan["copied"][turn].synchronize()  # the upload of two steps ago out of this pinned buffer (in practice long finished)
-        ent = plan["entries"]
-        b1, b2 = active[0][0]["betas"]
-        eps = active[0][0]["eps"]
-        grads = []
-        for i, (group, p) in enumerate(active):
-            if group["betas"] != (b1, b2) or group["eps"] != eps:
-                raise RuntimeError("NativeAdamW (fused): all param groups must share betas and eps")
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-            grads.append(g)
-            st = self._state_of(p)
-            st["step"] += 1
-            e = ent[i]
-            # every pointer of the record is re-read every step: load_state_dict(), model.to(), `p.data = ...` replace the
-            # parameter / moment tensors behind an unchanged id(p), and a cached address would then update freed memory
-            m, v = st["exp_avg"], st["exp_avg_sq"]
-            if not (m.is_contiguous() and v.is_contiguous() and p.is_contiguous()):
-                raise RuntimeError("NativeAdamW (fused): parameters and their moments must be contiguous")
-            if m.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32:
-                st["exp_avg"], st["exp_avg_sq"] = m, v = m.to(p.device, torch.float32), v.to(p.device, torch.float32)
-            e["w"], e["m"], e["v"], e["g"] = p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr()
-            if e["mode"] != 1:
-                e["mode"] = 0 if (p.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0) else 2
-            e["lr"], e["wd"] = group["lr"], group["weight_decay"]
-            e["bc1"] = 1.0 - b1 ** st["step"]
-            e["bc2_sqrt"] = (1.0 - b2 ** st["step"]) ** 0.5
-        host = plan["entries_host"][turn]
-        host.numpy()[:] = ent.view(np.uint8).reshape(-1)
-        plan["entries_dev"].copy_(host, non_blocking=True)
-        plan["copied"][turn] = torch.cuda.Event()
-        plan["copied"][turn].record()
-        stream = torch.cuda.current_stream().cuda_stream
-        gn, max_norm = 0, 0.0
-        if self.grad_clip_norm is not None:
-            acc = torch.zeros(1, dtype=torch.float32, device=plan["entries_dev"].device)
-            ws = torch.empty(plan["n_chunks"], dtype=torch.float32, device=acc.device) if self.deterministic else None
-            _lib.call("ocn_sumsq_multi", plan["entries_dev"].data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], acc.data_ptr(),
-                      0 if ws is None else ws.data_ptr(), stream)
-            self.last_grad_norm_sq = acc
-            gn, max_norm = acc.data_ptr(), float(self.grad_clip_norm)
-        _lib.call("ocn_adamw_multi", plan["entries_dev"].data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], float(b1), float(b2),
-                  float(eps), gn, max_norm, stream)
-        params = [p for _, p in active]
-        torch.autograd.graph.increment_version(params)  # raw-pointer update
-        for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launch
-            for c in self.weight_caches:
-                c.mark_fresh(p, n16, t16)
         return loss
+
+
+def nadam_schedule(step, mu_product, lr, beta1, beta2, momentum_decay):
+    """the host side of one NAdam step (torch/optim/nadam.py::_single_tensor_nadam), in Python floats: ``step`` is the 1-based number of the step
+    being taken, ``mu_product`` the running product after the step before (1.0 at the start).  Returns ``(mu_product, c_g, c_m, bc2)``: the new
+    product, the coefficients of ``g / den`` and ``m / den`` in the update, and ``1 - beta2^step`` (what ocn_nadamw_multi's record carries)."""
+    mu = beta1 * (1.0 - 0.5 * 0.96 ** (step * momentum_decay))
+    mu_next = beta1 * (1.0 - 0.5 * 0.96 ** ((step + 1) * momentum_decay))
+    mu_product = mu_product * mu
+    return mu_product, lr * (1.0 - mu) / (1.0 - mu_product), lr * mu_next / (1.0 - mu_product * mu_next), 1.0 - beta2 ** step
+
+
+class NativeNAdamW(_TableAdam):
+    """``torch.optim.NAdam(decoupled_weight_decay=True)`` -- the reference's ``--opt nadamw`` (optim.py:449-453) -- in NativeAdamW's one launch: fused
+    clip, refreshed operand copies, bit-reproducible with ``deterministic=True``.  The defaults are torch's; state keys are torch's (``step``,
+    ``mu_product``, ``exp_avg``, ``exp_avg_sq``; the two scalars are host numbers, a torch checkpoint's 0-d tensors are accepted).  ``lr`` is re-read
+    every step, a group's extra keys (``lr_scale``, ``group_name``, ...) are carried untouched; ``betas``, ``eps`` and ``momentum_decay`` are kernel
+    arguments and must agree across groups.  Only the decoupled form exists: the L2-coupled one is refused."""
+    _KERNEL, _WHO, _RECORD = "ocn_nadamw_multi", "NativeNAdamW", _NADAM_ENTRY
+    _SCALARS = {"step": (0, int), "mu_product": (1.0, float)}
+    _SHARED_TEXT = "betas, eps and momentum_decay"
+
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum_decay=4e-3, decoupled_weight_decay=True,
+                 grad_clip_norm=None, weight_caches=(), deterministic=False):
+        if not decoupled_weight_decay:
+            raise ValueError("NativeNAdamW: decoupled_weight_decay=False (L2-coupled NAdam) is not implemented; the reference's nadamw is the decoupled form")
+        if not (lr >= 0.0 and eps >= 0.0 and weight_decay >= 0.0 and momentum_decay >= 0.0 and 0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"NativeNAdamW: invalid hyper-parameters (lr={lr}, betas={betas}, eps={eps}, weight_decay={weight_decay}, "
+                             f"momentum_decay={momentum_decay})")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum_decay=momentum_decay,
+                                      decoupled_weight_decay=True))
+        self._setup(grad_clip_norm, weight_caches, deterministic)
+        self._schedule = (None, None)  # (step, mu_product, lr) -> nadam_schedule's result, the most recent one
+
+    def _shared_of(self, group):
+        if not group.get("decoupled_weight_decay", True):  # a loaded torch checkpoint of the L2-coupled form
+            raise RuntimeError("NativeNAdamW: a param group asks for decoupled_weight_decay=False, which is not implemented")
+        return super()._shared_of(group) + (float(group["momentum_decay"]),)
+
+    def _kernel_scalars(self, shared):
+        b1, b2, eps = shared[:3]
+        return 1.0 - b1, b2, 1.0 - b2, eps  # 1 - beta formed in double, as torch forms it (include/openclip_hip.h says what the fp32 difference costs)
+
+    def _fill(self, e, group, st, shared):
+        lr = group["lr"]
+        key = (st["step"], st["mu_product"], lr)
+        if key != self._schedule[0]:  # the parameters of a group (usually of the whole model) are at the same point of the schedule: evaluate it once
+            self._schedule = (key, nadam_schedule(*key, shared[0], shared[1], shared[3]))
+        st["mu_product"], e["c_g"], e["c_m"], e["bc2"] = self._schedule[1]
+        e["decay"] = 1.0 - lr * group["weight_decay"]
 
 
 # ---- Muon -------------------------------------------------------------------------------------------------------------------------------
 # Momentum + Newton-Schulz orthogonalisation for the 2-D hidden weights, AdamW for everything else (csrc/muon.hip states the arithmetic).
 NS_COEFFS = (3.4445, -4.7750, 2.0315)
 ADJUST_LR = ("match_rms_adamw", "original")
-DEFAULT_FALLBACK = ("token_embedding.weight", "positional_embedding", "visual.positional_embedding", "visual.class_embedding", "logit_scale", "logit_bias")
 _MUON_ENTRY = np.dtype([("g", "<u8"), ("buf", "<u8"), ("w", "<u8"), ("w16n", "<u8"), ("w16t", "<u8"), ("xn", "<u8"), ("xt", "<u8"), ("xfin", "<u8"),
                         ("rows", "<i4"), ("cols", "<i4"), ("ldn", "<i4"), ("ldt", "<i4"), ("chunk0", "<i4"), ("nchunks", "<i4"),
                         ("step", "<f4"), ("decay", "<f4")])
 assert _MUON_ENTRY.itemsize == 96
-
-
-def muon_param_groups(model, weight_decay, fallback_list=DEFAULT_FALLBACK):
-    """the reference's ``wd_param_groups(model, weight_decay, exclude_fn, fallback_fn)`` (optim.py:178-208) with ``fallback_fn`` built from
-    ``--opt-fallback-list``-style patterns (optim.py:392-394: ``fnmatch.fnmatchcase`` on the full parameter name): up to four groups keyed by
-    (no weight decay, fallback), named "no_wd" / "wd" (+ "/fallback"), the matched ones flagged ``use_fallback=True``.  The no-decay rule is
-    ``param_groups_like_reference``'s (1-D parameters and ``model.no_weight_decay()`` names)."""
-    import fnmatch
-    skip = set(model.no_weight_decay()) if hasattr(model, "no_weight_decay") else set()
-    patterns = tuple(fallback_list or ())
-    buckets = {}
-    for n, p in model.named_parameters():
-        if not p.requires_grad:
-            continue
-        n = n[len("module."):] if n.startswith("module.") else n
-        no_wd = p.ndim <= 1 or n in skip
-        fb = any(fnmatch.fnmatchcase(n, pat) for pat in patterns)
-        if (no_wd, fb) not in buckets:
-            group = {"params": [], "weight_decay": 0.0 if no_wd else weight_decay, "group_name": ("no_wd" if no_wd else "wd") + ("/fallback" if fb else "")}
-            if fb:
-                group["use_fallback"] = True
-            buckets[(no_wd, fb)] = group
-        buckets[(no_wd, fb)]["params"].append(p)
-    return list(buckets.values())
 
 
 def takes_muon(group, p):
@@ -257,27 +429,6 @@ def muon_lr_scale(adjust_lr, rows, cols):
 
 def _pad32(n):
     return (n + 31) // 32 * 32
-
-
-class _Table:
-    """a record table that travels host -> device every step through one of TWO pinned buffers used alternately (see NativeAdamW._build_plan)"""
-
-    def __init__(self, records, dev):
-        self.records = records
-        nbytes = records.size * records.dtype.itemsize
-        self.host = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.copied, self.turn = [None, None], 0
-
-    def upload(self):
-        turn, self.turn = self.turn, 1 - self.turn
-        if self.copied[turn] is not None and not self.copied[turn].query():
-            self.copied[turn].synchronize()
-        self.host[turn].numpy()[:] = self.records.view(np.uint8).reshape(-1)
-        self.dev.copy_(self.host[turn], non_blocking=True)
-        self.copied[turn] = torch.cuda.Event()
-        self.copied[turn].record()
-        return self.dev
 
 
 class NativeMuon(torch.optim.Optimizer):
@@ -505,3 +656,84 @@ class NativeMuon(torch.optim.Optimizer):
             for c in self.weight_caches:
                 c.mark_fresh(p, n16, t16)
         return loss
+
+
+# ---- create_optimizer (open_clip_train/optim.py:24-64, 336-472) ---------------------------------------------------------------------------
+@dataclass
+class OptimizerCfg:
+    """the reference's typed optimizer configuration, field for field (optim.py:51-64); ``create_optimizer`` reads it by attribute, so the
+    reference's own instance serves as well.  ``opt``: "adamw", "nadamw" or "muon"."""
+    opt: str = "adamw"
+    lr: float = 5e-4
+    weight_decay: float = 0.2
+    beta1: Optional[float] = None
+    beta2: Optional[float] = None
+    eps: Optional[float] = None
+    momentum: Optional[float] = None
+    opt_kwargs: dict = field(default_factory=dict)
+    text_layer_decay: Optional[float] = None
+    image_layer_decay: Optional[float] = None
+    audio_layer_decay: Optional[float] = None
+    pooler_in_head: bool = True
+    wd_exclude_patterns: List[str] = field(default_factory=list)
+    fallback_list: Optional[List[str]] = None
+
+
+def create_optimizer(model, cfg, device=None, tensorize=False, *, grad_clip_norm=None, deterministic=False):
+    """``open_clip_train.optim.create_optimizer(model, cfg, device, tensorize)`` for a ``NativeCLIP`` (possibly behind DDP / torch.compile): the
+    reference's parameter groups, the native optimizer ``cfg.opt`` names -- "adamw" -> NativeAdamW, "nadamw" -> NativeNAdamW, "muon" -> NativeMuon
+    (``cfg.fallback_list``, default ``DEFAULT_FALLBACK``, names its AdamW side) -- wired to the model's operand-copy caches, and every group's
+    initial ``lr = cfg.lr * lr_scale``.  ``grad_clip_norm`` / ``deterministic`` are native extras: the clip of train.py:181 fused into the step, and
+    the fixed-order norm.  Whatever the native path does not build raises by name."""
+    from .model import NativeCLIP
+    model = unwrap_model(model)
+    if not isinstance(model, NativeCLIP):
+        raise TypeError(f"open_clip_amd.create_optimizer groups a NativeCLIP (got {type(model).__name__}); other models go through "
+                        "open_clip_train.optim.create_optimizer")
+    if tensorize:
+        raise NotImplementedError("open_clip_amd.create_optimizer: tensorize=True (learning rates as device tensors, for torch.compile's step "
+                                  "strategy) is not implemented: the native optimizers read `lr` as a host float every step")
+    opt = cfg.opt.lower()
+    decays = {"text": getattr(cfg, "text_layer_decay", None), "image": getattr(cfg, "image_layer_decay", None),
+              "audio": getattr(cfg, "audio_layer_decay", None)}
+    for name, decay in decays.items():
+        if decay is not None and not (0.0 < decay <= 1.0):
+            raise ValueError(f"--{name}-layer-decay must be in (0, 1], got {decay}.")
+    decays = {name: (decay if decay and decay != 1.0 else None) for name, decay in decays.items()}
+    if decays["audio"] is not None:
+        raise ValueError(f"audio_layer_decay={decays['audio']}: a NativeCLIP has no audio tower (--audio-layer-decay applies to CLAP models)")
+    extra = dict(getattr(cfg, "opt_kwargs", None) or {})
+    fallback_list = getattr(cfg, "fallback_list", None) or extra.pop("fallback_list", None)
+    if opt.startswith("timm/"):
+        raise NotImplementedError(f"open_clip_amd.create_optimizer: the timm optimizer '{cfg.opt}' has no native counterpart (adamw, nadamw and muon "
+                                  "do); build it with open_clip_train.optim.create_optimizer")
+    if opt not in ("adamw", "nadamw", "muon"):
+        raise ValueError(f"Unknown optimizer {opt}")
+    if fallback_list and opt != "muon":
+        raise ValueError(f"fallback_list (--opt-fallback-list) only applies to a hybrid optimizer (muon), not '{cfg.opt}'.")
+    if opt == "muon":
+        fallback_list = fallback_list or DEFAULT_FALLBACK
+    exclude_fn = make_wd_exclude(model, getattr(cfg, "wd_exclude_patterns", None))
+    fallback_fn = make_fallback_fn(fallback_list)
+    if decays["text"] or decays["image"]:
+        groups = layer_decay_param_groups(model, cfg.weight_decay, decays["text"], decays["image"], getattr(cfg, "pooler_in_head", True), exclude_fn,
+                                          fallback_fn)
+    else:
+        groups = wd_param_groups(model, cfg.weight_decay, exclude_fn, fallback_fn)
+    if (cfg.beta1 is None) != (cfg.beta2 is None):
+        raise ValueError("BOTH beta1 and beta2 must be specified (or neither).")
+    kwargs = {"lr": cfg.lr}
+    if cfg.beta1 is not None:
+        kwargs["betas"] = (cfg.beta1, cfg.beta2)
+    if cfg.eps is not None:
+        kwargs["eps"] = cfg.eps
+    if opt == "muon" and getattr(cfg, "momentum", None) is not None:
+        kwargs["momentum"] = cfg.momentum
+    if opt != "muon":  # NativeMuon has no switch: its norm is always summed in a fixed order
+        kwargs["deterministic"] = deterministic
+    kwargs.update(weight_caches=weight_caches_of(model), grad_clip_norm=grad_clip_norm)
+    kwargs.update(extra)  # merged last, as the reference does
+    optimizer = {"adamw": NativeAdamW, "nadamw": NativeNAdamW, "muon": NativeMuon}[opt](groups, **kwargs)
+    for group in optimizer.param_groups:  # optim.py:461 / scheduler.py:6-15: layer decay holds before the first scheduler step
+        group["lr"] = cfg.lr * group.get("lr_scale", 1.0)
+    return optimizer

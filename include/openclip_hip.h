@@ -68,8 +68,9 @@ const char* ocn_last_error(void);
  *                  and the unsorted per-occurrence-atomic ocn_token_embed_bwd.
  *   110            Muon optimizer: new ocn_gemm_nt_batched, ocn_muon_momentum_multi, ocn_muon_normalize_multi, ocn_muon_apply_multi, ocn_muon_axpby
  *                  (no signature changed).
- *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed). */
-#define OCN_ABI_VERSION 111
+ *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed).
+ *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed). */
+#define OCN_ABI_VERSION 112
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -205,6 +206,20 @@ int ocn_attn_pooled_bwd(const void* q, const void* kv, const void* out, const vo
  *   of an image must be distinct and inside [0, G) -- an index outside is clamped by every kernel that reads keep, so no access leaves a buffer). */
 int ocn_patch_keep_plan(int64_t seed, int B, int G, int K, int32_t* keep, int32_t* inv, ocn_stream_t stream);
 int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int K, ocn_stream_t stream);
+
+/* ---- device-side RandomResizedCrop (transform.py:435-440: RandomResizedCrop(image_size, scale, interpolation=BICUBIC)) ----------------
+ * ocn_resized_crop_u8: src uint8 [B, Hs, Ws, 3] (HWC, what ocn_patchify_u8(hwc = 1) reads), boxes int32 [B, 4] = (top, left, height, width) ON THE
+ *   DEVICE, out uint8 [B, Ho, Wo, 3].  Crop, then antialiased bicubic resize, rounded once.  Per axis (box side n, output side m):
+ *   scale = n / m, support = 2 max(scale, 1), inv = 1 / max(scale, 1); output o: center = scale (o + 0.5), taps k in
+ *   [max(0, int(center - support + 0.5)), min(n, int(center + support + 0.5))) with weight cubic((k - center + 0.5) inv) (Keys' cubic, a = -0.5),
+ *   divided by their sum; taps are clamped to the crop, not to the source.  out = round(clamp(sum_y sum_x wy wx pixel, 0, 255)), summed in fp32,
+ *   ties to even: F.interpolate(crop.float(), (Ho, Wo), mode="bicubic", antialias=True, align_corners=False), clamped and rounded.  It is NOT
+ *   bit-compatible with PIL's fixed-point resampler (8-bit intermediate): the two differ by at most one level on roughly a sixth of noise values.
+ *   1 <= Ho, Wo <= 1024 and 1 <= Hs, Ws <= 8192, refused before any launch.  The boxes are never read back, so the kernel makes a bad one harmless:
+ *   a side is forced into [1, 4 * output side] (box anchored at its top-left corner; at most 17 taps per axis) and every source coordinate into the
+ *   image (a box that reaches outside reads the edge pixel repeated) -- no access leaves src whatever boxes holds.  The host-side builders
+ *   (input_pipeline.random_resized_crop_boxes / check_boxes) never produce either form. */
+int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
 
 /* ---- image tower embedding (transformer.py:793-808) -------------------------------------------
  * All four take the patches of a patch-dropout step as an optional index map, G = gh*gw = (H/P)*(W/P) patches per image of which K are embedded:

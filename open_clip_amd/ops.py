@@ -382,6 +382,29 @@ def patchify_u8(image, P, Kpad, mean, std, hwc, keep=None):
     return out
 
 
+def resized_crop_u8(src, boxes, size, out=None):
+    """crop + antialiased bicubic resize on the device (ocn_resized_crop_u8): ``src`` uint8 [B, Hs, Ws, 3], ``boxes`` int32 [B, 4] =
+    (top, left, height, width) on the same device, ``size`` an int or (Ho, Wo) -> uint8 [B, Ho, Wo, 3] (``out`` when given).  The box contents are
+    not checked here (they are device data; ``input_pipeline.check_boxes`` checks them on the host): the kernel clamps a bad box."""
+    Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if src.dtype != torch.uint8:
+        raise RuntimeError(f"resized_crop_u8: 'src' must be uint8 (got {src.dtype})")
+    if src.dim() != 4 or src.shape[3] != 3:
+        raise RuntimeError(f"resized_crop_u8: 'src' must be [B, Hs, Ws, 3] (channels last, 3 channels; got {tuple(src.shape)})")
+    B, Hs, Ws = src.shape[0], src.shape[1], src.shape[2]
+    if boxes.dim() != 2 or tuple(boxes.shape) != (B, 4):
+        raise RuntimeError(f"resized_crop_u8: 'boxes' must be int32 [B = {B}, 4] = (top, left, height, width) (got {tuple(boxes.shape)})")
+    sp, bp = _chk(src, torch.uint8, "src"), _chk(boxes, torch.int32, "boxes")
+    if boxes.device != src.device:
+        raise RuntimeError(f"resized_crop_u8: 'boxes' ({boxes.device}) and 'src' ({src.device}) must be on one device")
+    if out is None:
+        out = empty((B, Ho, Wo, 3), torch.uint8, src)
+    elif tuple(out.shape) != (B, Ho, Wo, 3) or out.device != src.device:
+        raise RuntimeError(f"resized_crop_u8: 'out' must be uint8 {(B, Ho, Wo, 3)} on {src.device} (got {tuple(out.shape)} on {out.device})")
+    _lib.call("ocn_resized_crop_u8", sp, B, Hs, Ws, bp, _chk(out, torch.uint8, "out"), Ho, Wo, _stream())
+    return out
+
+
 def embed_assemble_fwd(patch_out, cls, pos, B, G, C, keep=None):
     """emb fp32 [B * (K + 1), C]: class token + position 0, then patch_out[b*K + j] + pos[1 + keep[b, j]] (``keep`` None: all G patches in order)"""
     kp, K = _chk_keep(keep, B, G)

@@ -69,8 +69,9 @@ const char* ocn_last_error(void);
  *   110            Muon optimizer: new ocn_gemm_nt_batched, ocn_muon_momentum_multi, ocn_muon_normalize_multi, ocn_muon_apply_multi, ocn_muon_axpby
  *                  (no signature changed).
  *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed).
- *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed). */
-#define OCN_ABI_VERSION 112
+ *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed).
+ *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed). */
+#define OCN_ABI_VERSION 113
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -220,6 +221,42 @@ int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int 
  *   image (a box that reaches outside reads the edge pixel repeated) -- no access leaves src whatever boxes holds.  The host-side builders
  *   (input_pipeline.random_resized_crop_boxes / check_boxes) never produce either form. */
 int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
+
+/* ---- device-side colour jitter and grayscale (transform.py:335-364, :442-450: color_jitter(*aug_cfg.color_jitter, p), gray_scale(p)) ----------
+ * ocn_color_jitter_u8: img uint8 [B, H, W, 3] (HWC), factors fp32 [B, 4] = (brightness, contrast, saturation, hue) and plan int32 [B] ON THE DEVICE,
+ *   mean_ws fp32 [B] (workspace: the contrast means), out uint8 [B, H, W, 3]; out == img (in place) is allowed, any other overlap is not.
+ *   plan[b]: bits 0-11 = four 3-bit step codes executed from the low bits up (0 nothing, 1 brightness, 2 contrast, 3 saturation, 4 hue; 5-7 are
+ *   treated as nothing), bit 12 = grayscale behind the steps.  A code of 0 is how "this step is absent" is written (torchvision drops a step whose
+ *   range is degenerate); a jitter that was not applied is four zeros.  factors[b] is read by code, whatever the order of the steps.
+ *   THE ARITHMETIC (ours: torchvision's tensor path on a float image -- F.adjust_brightness / contrast / saturation / hue, F.rgb_to_grayscale -- with
+ *   ONE rounding at the end; no bit-compatibility with torchvision's uint8 path or PIL's ImageEnhance is claimed: those quantise to 8 bits after
+ *   every step, PIL rounds the grayscale weights to 16-bit integers and turns the hue of an 8-bit HSV image).  Per image, in fp32, x = u8 / 255 per
+ *   channel, gray(x) = 0.2989 r + 0.587 g + 0.114 b; every step ends in clamp(., 0, 1):
+ *     brightness f: x <- f x.
+ *     contrast f:   x <- f x + (1 - f) m, m = the mean of gray(x) over all pixels of the image as it stands when the (first) contrast step is
+ *                   reached: the steps in front of it applied, their clamps included.  The kernel sums gray rounded to multiples of 2^-24 in
+ *                   integers (m is within 2^-25 of the mean of the fp32 grays): the sum does not depend on the order of its terms, so m does not
+ *                   depend on the launch or on the alignment of the image.  No float atomics.
+ *     saturation f: x <- f x + (1 - f) gray(x), per pixel.
+ *     hue h in [-0.5, 0.5]: rgb -> hsv, hh <- (hh + h) mod 1 in [0, 1), hsv -> rgb, with
+ *       rgb -> hsv: maxc, minc, cr = maxc - minc, eq = (maxc == minc); s = cr / (eq ? 1 : maxc); (rc, gc, bc) = (maxc - (r, g, b)) / (eq ? 1 : cr);
+ *                   hh = [maxc == r] (bc - gc) + [maxc == g and maxc != r] (2 + rc - bc) + [maxc != g and maxc != r] (4 + gc - rc);
+ *                   hh <- fmod(hh / 6 + 1, 1); v = maxc;
+ *       hsv -> rgb: i = floor(6 hh), f = 6 hh - i, i <- i mod 6; p = clamp(v (1 - s)), q = clamp(v (1 - s f)), t = clamp(v (1 - s (1 - f)));
+ *                   (r, g, b) = (v,t,p) (q,v,p) (p,v,t) (p,q,v) (t,p,v) (v,p,q) for i = 0..5.
+ *     grayscale (bit 12): r = g = b <- gray(x).
+ *     out = round-half-even(255 x), the one rounding (torchvision truncates 255.999 x; this rounds, as the crop does).
+ *   The kernel multiplies by the rounded reciprocals of 255 and 6 and takes 1 / maxc and 1 / cr from v_rcp_f32 (1 ulp); results are judged against a
+ *   float64 evaluation of the above with a band of 2^-9 levels around .5 (tests/color_jitter_util.py).
+ *   An image whose plan holds no step and no grayscale comes out BIT-IDENTICAL: it is copied, not run through identity factors (the hue round
+ *   trip is not exact in fp32 even at h = 0); in place it is not touched at all.
+ *   Two launches: the contrast means (one workgroup per image with a contrast step), then the chain per pixel; a thread owns 4 consecutive pixels =
+ *   12 bytes = three dwords where the image's address allows, single pixels by bytes in front of and behind them, the same arithmetic either way.
+ *   1 <= H, W <= 8192, refused before any launch.  NO ADDRESS DEPENDS ON factors OR plan: whatever they hold, exactly B * H * W * 3 bytes are read and
+ *   written; non-finite factors give unspecified pixel values and nothing else.  The host-side builders (input_pipeline.color_jitter_plan /
+ *   check_jitter) produce neither a code above 4, a step twice, nor a non-finite factor. */
+int ocn_color_jitter_u8(const void* img_u8, int B, int H, int W, const float* factors, const int32_t* plan, float* mean_ws, void* out_u8,
+                        ocn_stream_t stream);
 
 /* ---- image tower embedding (transformer.py:793-808) -------------------------------------------
  * All four take the patches of a patch-dropout step as an optional index map, G = gh*gw = (H/P)*(W/P) patches per image of which K are embedded:

@@ -27,7 +27,18 @@ compute stream.  Nothing comes back to the host:
     pipe.submit(u8_source_host, text_host)       # boxes drawn here (crop_generator makes them reproducible); boxes=... for fixed ones
     batch = pipe.next()                          # batch["image"]: uint8 [B, 224, 224, 3] of this step, batch["boxes"]: device int32 [B, 4]
 
-PyTorch is plumbing here (pinned allocations, streams, events); the only arithmetic in this file is the box sampling, B small integers per batch."""
+With ``color_jitter_prob`` / ``gray_scale_prob`` the two remaining steps of that transform branch, ``color_jitter(*aug_cfg.color_jitter, p)`` and
+``gray_scale(p)`` (``transform.py:335-364``, ``:442-450``), run on the device as well, behind the crop as in the reference: ``submit()`` draws per-image
+factors, a step order and the grayscale bit on the host (``color_jitter_plan``, or takes the caller's ``jitter=(factors, plan)``), they travel with the
+batch and ``next()`` runs ``ops.color_jitter_u8`` -- in place on the crop's fresh output, into a new tensor when there is no crop (the slot is never
+modified).  ``from_aug_cfg`` builds the pipeline from the reference's ``AugmentationCfg`` fields:
+
+    pipe = DeviceBatchPipeline.from_aug_cfg(device, (B, 256, 256, 3), (B, 77), 224, {"scale": (0.9, 1.0), "color_jitter": (0.4, 0.4, 0.4, 0.1),
+                                                                                   "color_jitter_prob": 0.8, "gray_scale_prob": 0.2})
+    batch = pipe.next()                          # batch["jitter"]: device (factors float32 [B, 4], plan int32 [B]) the image was run with
+
+PyTorch is plumbing here (pinned allocations, streams, events); the only arithmetic in this file is the sampling of boxes and jitter parameters, a few
+small numbers per image."""
 import math
 
 import torch
@@ -84,6 +95,90 @@ def check_boxes(boxes, Hs, Ws, size):
             raise ValueError(f"check_boxes: box {i} = {tuple(b[i].tolist())} (top, left, height, width) {what}")
 
 
+JITTER_STEPS = ("brightness", "contrast", "saturation", "hue")  # step code k + 1 in a plan entry, column k of factors
+JITTER_GRAY_BIT = 1 << 12
+_JITTER_IDENTITY = (1.0, 1.0, 1.0, 0.0)
+
+
+def _jitter_ranges(color_jitter):
+    """torchvision's ``ColorJitter._check_input`` for (brightness, contrast, saturation, hue): each entry a float v -- [max(0, 1 - v), 1 + v] for the
+    first three, [-v, v] with 0 <= v <= 0.5 for hue -- or a (min, max) pair; a range that is the identity alone means the step is absent (None)"""
+    if color_jitter is None or isinstance(color_jitter, (int, float)) or len(color_jitter) != 4:
+        raise ValueError(f"color_jitter must have 4 entries (brightness, contrast, saturation, hue) when color_jitter_prob is set (got {color_jitter!r})")
+    ranges = []
+    for name, value in zip(JITTER_STEPS, color_jitter):
+        hue = name == "hue"
+        center, lo_bound, hi_bound = (0.0, -0.5, 0.5) if hue else (1.0, 0.0, math.inf)
+        if isinstance(value, (int, float)):
+            if value < 0:
+                raise ValueError(f"color_jitter: {name} = {value} must not be negative")
+            lo, hi = center - float(value), center + float(value)
+            if not hue:
+                lo = max(lo, 0.0)
+        elif len(value) == 2:
+            lo, hi = float(value[0]), float(value[1])
+        else:
+            raise ValueError(f"color_jitter: {name} must be a number or a (min, max) pair (got {value!r})")
+        if not (lo_bound <= lo <= hi <= hi_bound):
+            raise ValueError(f"color_jitter: {name} range ({lo}, {hi}) must be ordered and lie in [{lo_bound}, {hi_bound}]")
+        ranges.append(None if lo == hi == center else (lo, hi))
+    return ranges
+
+
+def color_jitter_plan(B, color_jitter, color_jitter_prob, gray_scale_prob, generator=None):
+    """The parameters of ``ops.color_jitter_u8`` for B images, drawn by the rule of torchvision's ``ColorJitter.get_params`` per image, vectorised in
+    torch on the CPU: host (factors float32 [B, 4], plan int32 [B]) in the layout of include/openclip_hip.h.  ``color_jitter`` = (brightness, contrast,
+    saturation, hue), each a float v (factor uniform in [max(0, 1 - v), 1 + v]; hue uniform in [-v, v], 0 <= v <= 0.5; v = 0: the step is absent) or a
+    (min, max) pair; the present steps run in a uniformly random order; the jitter as a whole is applied with probability ``color_jitter_prob`` (an
+    image without it has four zero step codes) and grayscale with probability ``gray_scale_prob`` (None or 0: never).  As in the reference
+    (transform.py:442-443) a truthy ``color_jitter_prob`` needs a 4-entry ``color_jitter``, and without it ``color_jitter`` is ignored.  The factor of
+    a step that is not in an image's plan is the identity (1, 1, 1, 0).  Reproducible under ``generator``; it does NOT reproduce torchvision's or
+    Python's random streams (other draws, other order)."""
+    ranges = _jitter_ranges(color_jitter) if color_jitter_prob else [None] * 4
+    u = torch.rand((10, B), dtype=torch.float64, generator=generator)  # 0-3 factors, 4-7 order keys, 8 jitter or not, 9 grayscale or not
+    applied = u[8] < float(color_jitter_prob or 0.0)
+    factors = torch.empty((B, 4), dtype=torch.float64)
+    keys = u[4:8].t().clone()
+    for k, rng in enumerate(ranges):
+        if rng is None:
+            factors[:, k] = _JITTER_IDENTITY[k]
+            keys[:, k] = 2.0  # behind every present step
+        else:
+            factors[:, k] = torch.where(applied, rng[0] + (rng[1] - rng[0]) * u[k], torch.tensor(_JITTER_IDENTITY[k], dtype=torch.float64))
+    order = torch.argsort(keys, dim=1, stable=True)  # the present steps first, in the order of their keys: a uniform permutation
+    present = torch.tensor([r is not None for r in ranges])
+    codes = torch.where(present[order] & applied[:, None], order + 1, torch.zeros_like(order))
+    plan = (codes << (3 * torch.arange(4))[None, :]).sum(dim=1)
+    plan = plan + JITTER_GRAY_BIT * (u[9] < float(gray_scale_prob or 0.0)).long()
+    return factors.to(torch.float32), plan.to(torch.int32)
+
+
+def check_jitter(factors, plan):
+    """host-side check of colour jitter parameters (factors float32 [B, 4], plan int32 [B]; layout in include/openclip_hip.h): ValueError for a wrong
+    shape or dtype, a non-finite factor, a negative brightness / contrast / saturation factor, |hue| > 0.5, a step code above 4, a step that appears
+    twice, or bits above the grayscale bit -- naming the image"""
+    if factors.is_cuda or plan.is_cuda:
+        raise ValueError("check_jitter: a host-side check (the parameters of a device tensor are never read back)")
+    if factors.dtype != torch.float32 or factors.dim() != 2 or factors.shape[1] != 4:
+        raise ValueError(f"check_jitter: expected float32 factors [B, 4] = (brightness, contrast, saturation, hue), got {factors.dtype} {tuple(factors.shape)}")
+    if plan.dtype != torch.int32 or tuple(plan.shape) != (factors.shape[0],):
+        raise ValueError(f"check_jitter: expected an int32 plan [B = {factors.shape[0]}], got {plan.dtype} {tuple(plan.shape)}")
+    p = plan.long()
+    codes = torch.stack([(p >> (3 * k)) & 7 for k in range(4)], dim=1)
+    twice = torch.zeros(plan.shape[0], dtype=torch.bool)
+    for c in range(1, 5):
+        twice |= (codes == c).sum(dim=1) > 1
+    for bad, what in ((~torch.isfinite(factors).all(dim=1), "has a factor that is not finite"),
+                      ((factors[:, :3] < 0).any(dim=1), "has a negative brightness, contrast or saturation factor"),
+                      (factors[:, 3].abs() > 0.5, "has a hue shift outside [-0.5, 0.5]"),
+                      ((codes > 4).any(dim=1), "has a step code above 4"),
+                      (twice, "has a step twice"),
+                      ((p < 0) | (p >= 2 * JITTER_GRAY_BIT), "has bits above the grayscale bit")):
+        if bool(bad.any()):
+            i = int(bad.int().argmax())
+            raise ValueError(f"check_jitter: image {i} (factors {tuple(factors[i].tolist())}, plan {int(p[i]):#x}) {what}")
+
+
 class HostTextPlan:
     """The packed layout of one text batch (``model._TextPack``: only the tokens up to the pooled EOT exist in the text tower) computed on
     the HOST, where the tokens come from anyway (the tokenizer's output in the loader), so that the step never has to read the packed row
@@ -132,17 +227,27 @@ class HostTextPlan:
 
 class DeviceBatchPipeline:
     def __init__(self, device, image_shape, text_shape, depth: int = 2, image_dtype=torch.uint8, plan_text_vocab=None, attn_buckets=True,
-                 crop_size=None, crop_scale=(0.9, 1.0), crop_ratio=(3 / 4, 4 / 3), crop_generator=None):
+                 crop_size=None, crop_scale=(0.9, 1.0), crop_ratio=(3 / 4, 4 / 3), crop_generator=None,
+                 color_jitter=None, color_jitter_prob=None, gray_scale_prob=None, jitter_generator=None):
         """``plan_text_vocab`` = the model's vocab_size: every submitted batch also carries its packed text layout computed on the host
         (``HostTextPlan``), attached to the device text tensor; ``NativeCLIP`` then runs the step without any host synchronisation.
         ``crop_size`` (int or (Ho, Wo)): ``image_shape`` is the SOURCE shape [B, Hs, Ws, 3] and every batch is cropped and resized to
         ``crop_size`` on the device, one box per image drawn by ``random_resized_crop_boxes(B, Hs, Ws, crop_scale, crop_ratio, crop_generator)``
-        (a host ``torch.Generator``) unless ``submit(boxes=...)`` brings its own."""
+        (a host ``torch.Generator``) unless ``submit(boxes=...)`` brings its own.
+        ``color_jitter_prob`` / ``gray_scale_prob`` (either one truthy; with or without ``crop_size``): every batch also goes through the train
+        transform's colour jitter and grayscale on the device, behind the crop (transform.py:442-450), with per-image parameters drawn by
+        ``color_jitter_plan(B, color_jitter, color_jitter_prob, gray_scale_prob, jitter_generator)`` unless ``submit(jitter=...)`` brings its own."""
         self.device = torch.device(device)
         self.depth = depth
         self.crop_size, self.crop_scale, self.crop_ratio, self.crop_generator = crop_size, crop_scale, crop_ratio, crop_generator
         if crop_size is not None and (len(image_shape) != 4 or image_shape[3] != 3 or image_dtype != torch.uint8):
             raise ValueError(f"DeviceBatchPipeline: crop_size needs uint8 source images [B, Hs, Ws, 3] (got {image_dtype} {tuple(image_shape)})")
+        self.color_jitter, self.color_jitter_prob, self.gray_scale_prob, self.jitter_generator = color_jitter, color_jitter_prob, gray_scale_prob, jitter_generator
+        self.jitter = bool(color_jitter_prob) or bool(gray_scale_prob)
+        if self.jitter and (len(image_shape) != 4 or image_shape[3] != 3 or image_dtype != torch.uint8):
+            raise ValueError(f"DeviceBatchPipeline: colour jitter / grayscale need uint8 images [B, H, W, 3] (got {image_dtype} {tuple(image_shape)})")
+        if color_jitter_prob:
+            _jitter_ranges(color_jitter)  # a bad color_jitter is refused here, not at the first submit
         self.plan_text_vocab, self.attn_buckets = plan_text_vocab, attn_buckets
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.slots = []
@@ -162,9 +267,37 @@ class DeviceBatchPipeline:
             if crop_size is not None:
                 self.slots[-1].update(boxes=torch.empty((image_shape[0], 4), dtype=torch.int32, device=self.device),
                                       h_boxes=torch.empty((image_shape[0], 4), dtype=torch.int32).pin_memory())
+            if self.jitter:
+                self.slots[-1].update(jit_factors=torch.empty((image_shape[0], 4), dtype=torch.float32, device=self.device),
+                                      jit_plan=torch.empty((image_shape[0],), dtype=torch.int32, device=self.device),
+                                      h_jit_factors=torch.empty((image_shape[0], 4), dtype=torch.float32).pin_memory(),
+                                      h_jit_plan=torch.empty((image_shape[0],), dtype=torch.int32).pin_memory())
         self._w = 0      # next slot to fill
         self._r = 0      # next slot to hand out
         self._queued = 0
+
+    @classmethod
+    def from_aug_cfg(cls, device, image_shape, text_shape, image_size, aug_cfg, **kw):
+        """the pipeline of the reference's non-timm train transform (``image_transform(is_train=True, aug_cfg=...)``, transform.py:431-455) for
+        ``aug_cfg`` = a dict or any object with the fields of its ``AugmentationCfg`` (transform.py:63-75): ``scale`` and ``ratio`` become the crop to
+        ``image_size`` (``image_shape`` is the SOURCE shape), ``color_jitter`` / ``color_jitter_prob`` / ``gray_scale_prob`` the jitter and grayscale
+        behind it; ``kw`` goes to the constructor (depth, plan_text_vocab, crop_generator, jitter_generator, ...).  ``use_timm``, ``naflex``,
+        ``re_prob`` and ``re_count`` are not implemented and are refused by name.  One difference: the reference's non-timm branch silently ignores
+        ``ratio`` (RandomResizedCrop's default 3/4 - 4/3 is used); here a ``ratio`` that is set is honoured."""
+        fields = ("scale", "ratio", "color_jitter", "re_prob", "re_count", "naflex", "use_timm", "color_jitter_prob", "gray_scale_prob")
+        if isinstance(aug_cfg, dict):
+            unknown = sorted(set(aug_cfg) - set(fields))
+            if unknown:
+                raise TypeError(f"from_aug_cfg: unknown aug_cfg field(s) {unknown} (AugmentationCfg has {list(fields)})")
+            get = aug_cfg.get
+        else:
+            get = lambda k: getattr(aug_cfg, k, None)  # noqa: E731
+        for name in ("use_timm", "naflex", "re_prob", "re_count"):
+            if get(name):
+                raise NotImplementedError(f"from_aug_cfg: aug_cfg.{name} = {get(name)!r} (the timm augmentations) is not implemented on the device path")
+        return cls(device, image_shape, text_shape, crop_size=image_size, crop_scale=tuple(get("scale") or (0.9, 1.0)),
+                   crop_ratio=tuple(get("ratio") or (3 / 4, 4 / 3)), color_jitter=get("color_jitter"), color_jitter_prob=get("color_jitter_prob"),
+                   gray_scale_prob=get("gray_scale_prob"), **kw)
 
     def staging(self):
         """the pinned host buffers of the slot the next ``submit`` will use -- a loader can decode straight into them and
@@ -174,11 +307,12 @@ class DeviceBatchPipeline:
             s["host_done"].synchronize()  # the previous transfer out of this pinned buffer has finished
         return s["h_image"], s["h_text"]
 
-    def submit(self, image_host=None, text_host=None, boxes=None):
+    def submit(self, image_host=None, text_host=None, boxes=None, jitter=None):
         """enqueue host -> device of one batch on the copy stream.  ``image_host`` / ``text_host`` = any host tensors (copied into
         the slot's pinned staging buffers first) or None when the caller filled ``staging()`` in place.  ``boxes`` (with ``crop_size`` only):
         the caller's crop boxes, host integers [B, 4] = (top, left, height, width), checked by ``check_boxes`` -- fixed boxes for evaluation;
-        None draws them."""
+        None draws them.  ``jitter`` (with ``color_jitter_prob`` / ``gray_scale_prob`` only): the caller's (factors float32 [B, 4], plan int32 [B])
+        on the host, checked by ``check_jitter``; None draws them."""
         if self._queued == self.depth:
             raise RuntimeError("DeviceBatchPipeline: all slots are in flight; call next() / release() first")
         s = self.slots[self._w]
@@ -191,6 +325,15 @@ class DeviceBatchPipeline:
             elif tuple(boxes.shape) != (B, 4):
                 raise ValueError(f"DeviceBatchPipeline: boxes must be [B = {B}, 4] (got {tuple(boxes.shape)})")
             check_boxes(boxes, Hs, Ws, self.crop_size)
+        if jitter is not None and not self.jitter:
+            raise ValueError("DeviceBatchPipeline: jitter= needs a pipeline built with color_jitter_prob or gray_scale_prob")
+        if self.jitter:
+            B = s["image"].shape[0]
+            if jitter is None:
+                jitter = color_jitter_plan(B, self.color_jitter, self.color_jitter_prob, self.gray_scale_prob, self.jitter_generator)
+            check_jitter(*jitter)
+            if jitter[0].shape[0] != B:
+                raise ValueError(f"DeviceBatchPipeline: jitter must be (factors [B = {B}, 4], plan [B = {B}]) (got {tuple(jitter[0].shape)}, {tuple(jitter[1].shape)})")
         src_i, src_t = s["h_image"], s["h_text"]
         if image_host is not None:
             if image_host.is_pinned() and text_host.is_pinned():
@@ -211,6 +354,11 @@ class DeviceBatchPipeline:
             if s["host_done"] is not None and not s["host_done"].query():
                 s["host_done"].synchronize()  # as for the plan: the slot's previous transfer may still read the pinned boxes
             s["h_boxes"].copy_(boxes)
+        if self.jitter:
+            if s["host_done"] is not None and not s["host_done"].query():
+                s["host_done"].synchronize()  # as for the boxes
+            s["h_jit_factors"].copy_(jitter[0])
+            s["h_jit_plan"].copy_(jitter[1])
         with torch.cuda.stream(self.copy_stream):
             self.copy_stream.wait_event(s["free"])  # the forward that read this slot last has consumed it
             s["image"].copy_(src_i, non_blocking=True)
@@ -221,6 +369,9 @@ class DeviceBatchPipeline:
                 s["plan_tokens"][:plan.M].copy_(s["h_plan_tokens"][:plan.M], non_blocking=True)
             if self.crop_size is not None:
                 s["boxes"].copy_(s["h_boxes"], non_blocking=True)
+            if self.jitter:
+                s["jit_factors"].copy_(s["h_jit_factors"], non_blocking=True)
+                s["jit_plan"].copy_(s["h_jit_plan"], non_blocking=True)
             s["ready"].record(self.copy_stream)
             s["host_done"] = s["ready"]
         self._w = (self._w + 1) % self.depth
@@ -229,7 +380,9 @@ class DeviceBatchPipeline:
     def next(self):
         """device batch ``{'image': uint8 [B,H,W,3], 'text': int64 [B,L]}`` of the oldest submitted slot; the current stream is made
         to wait for its copy (no host synchronisation).  With ``crop_size``, 'image' is the cropped and resized batch uint8 [B,Ho,Wo,3], a tensor
-        of this step written by ``ops.resized_crop_u8`` on the current stream, and 'boxes' the device int32 [B,4] it was cut with."""
+        of this step written by ``ops.resized_crop_u8`` on the current stream, and 'boxes' the device int32 [B,4] it was cut with.  With colour jitter /
+        grayscale, 'image' has gone through ``ops.color_jitter_u8`` (in place on the crop's fresh output; into a new tensor without ``crop_size``: the
+        slot's pixels are never modified) and 'jitter' is the device (factors float32 [B,4], plan int32 [B]) it was run with."""
         if self._queued == 0:
             raise RuntimeError("DeviceBatchPipeline: nothing submitted")
         s = self.slots[self._r]
@@ -247,8 +400,14 @@ class DeviceBatchPipeline:
             text._ocn_host_plan = plan.device_views(s["plan_ints"][:plan.ints.numel()].clone(), s["plan_tokens"][:plan.M].clone())
         if self.crop_size is not None:  # reads the slot's pixels and boxes on the compute stream, ahead of any release(): the slot's 'free' event orders
             boxes = s["boxes"].clone()  # the copy stream's next overwrite behind it
-            return {"image": ops.resized_crop_u8(s["image"], boxes, self.crop_size), "text": text, "boxes": boxes, "_slot": s}
-        return {"image": s["image"], "text": text, "_slot": s}
+            batch = {"image": ops.resized_crop_u8(s["image"], boxes, self.crop_size), "text": text, "boxes": boxes, "_slot": s}
+        else:
+            batch = {"image": s["image"], "text": text, "_slot": s}
+        if self.jitter:  # the reference's order: crop, jitter, grayscale.  The parameters leave the slot like the boxes
+            factors, plan = s["jit_factors"].clone(), s["jit_plan"].clone()
+            batch["image"] = ops.color_jitter_u8(batch["image"], factors, plan, out=batch["image"] if self.crop_size is not None else None)
+            batch["jitter"] = (factors, plan)
+        return batch
 
     def release(self, batch):
         """call once the forward that reads ``batch`` has been enqueued: the slot's pixels are read by the patch kernel only, and everything

@@ -405,6 +405,32 @@ def resized_crop_u8(src, boxes, size, out=None):
     return out
 
 
+def color_jitter_u8(img, factors, plan, out=None):
+    """colour jitter + grayscale on the device (ocn_color_jitter_u8; the arithmetic is defined in include/openclip_hip.h): ``img`` uint8 [B, H, W, 3],
+    ``factors`` float32 [B, 4] = (brightness, contrast, saturation, hue) and ``plan`` int32 [B] (four 3-bit step codes from the low bits up, bit 12 =
+    grayscale) on the same device -> uint8 [B, H, W, 3]: a new tensor, or ``out`` when given (``out=img`` works in place).  The parameters are not
+    checked here (they are device data; ``input_pipeline.check_jitter`` checks them on the host): the kernel takes no address from them."""
+    if img.dtype != torch.uint8:
+        raise RuntimeError(f"color_jitter_u8: 'img' must be uint8 (got {img.dtype})")
+    if img.dim() != 4 or img.shape[3] != 3:
+        raise RuntimeError(f"color_jitter_u8: 'img' must be [B, H, W, 3] (channels last, 3 channels; got {tuple(img.shape)})")
+    B, H, W = img.shape[0], img.shape[1], img.shape[2]
+    if tuple(factors.shape) != (B, 4):
+        raise RuntimeError(f"color_jitter_u8: 'factors' must be float32 [B = {B}, 4] = (brightness, contrast, saturation, hue) (got {tuple(factors.shape)})")
+    if tuple(plan.shape) != (B,):
+        raise RuntimeError(f"color_jitter_u8: 'plan' must be int32 [B = {B}] (got {tuple(plan.shape)})")
+    ip, fp, pp = _chk(img, torch.uint8, "img"), _chk(factors, F32, "factors"), _chk(plan, torch.int32, "plan")
+    if factors.device != img.device or plan.device != img.device:
+        raise RuntimeError(f"color_jitter_u8: 'factors' ({factors.device}), 'plan' ({plan.device}) and 'img' ({img.device}) must be on one device")
+    if out is None:
+        out = empty((B, H, W, 3), torch.uint8, img)
+    elif tuple(out.shape) != (B, H, W, 3) or out.device != img.device:
+        raise RuntimeError(f"color_jitter_u8: 'out' must be uint8 {(B, H, W, 3)} on {img.device} (got {tuple(out.shape)} on {out.device})")
+    mean_ws = empty((B,), F32, img)  # the contrast means: written by the first launch, read by the second
+    _lib.call("ocn_color_jitter_u8", ip, B, H, W, fp, pp, _chk(mean_ws, F32, "mean_ws"), _chk(out, torch.uint8, "out"), _stream())
+    return out
+
+
 def embed_assemble_fwd(patch_out, cls, pos, B, G, C, keep=None):
     """emb fp32 [B * (K + 1), C]: class token + position 0, then patch_out[b*K + j] + pos[1 + keep[b, j]] (``keep`` None: all G patches in order)"""
     kp, K = _chk_keep(keep, B, G)

@@ -70,8 +70,9 @@ const char* ocn_last_error(void);
  *                  (no signature changed).
  *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed).
  *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed).
- *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed). */
-#define OCN_ABI_VERSION 113
+ *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed).
+ *   114            ragged sources and the validation transform on the device: new ocn_resample_u8 (no signature changed). */
+#define OCN_ABI_VERSION 114
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -221,6 +222,32 @@ int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int 
  *   image (a box that reaches outside reads the edge pixel repeated) -- no access leaves src whatever boxes holds.  The host-side builders
  *   (input_pipeline.random_resized_crop_boxes / check_boxes) never produce either form. */
 int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
+
+/* ---- device-side resampling of ragged sources: the train crop and the validation transform in one form -------------------------------------
+ * (transform.py:435-440 RandomResizedCrop; :461-492 image_transform(is_train=False): Resize / ResizeKeepRatio + CenterCrop / CenterCropOrPad)
+ * ocn_resample_u8: arena uint8 [arena_bytes], one device buffer (base 16-byte aligned, arena_bytes a positive multiple of 4); offsets int64 [B] ON THE
+ *   DEVICE = the byte offset of image b in the arena, a multiple of 16; image b is HWC uint8, tightly packed, Hs * Ws * 3 bytes; plan int32 [B, 10]
+ *   ON THE DEVICE = (Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox); out uint8 [B, Ho, Wo, 3]; fill in [0, 255], written to all three channels.
+ *   Per axis (y shown, x alike): output row o is row r = o + oy of the image virtually resized to Rh rows; r < 0 or r >= Rh: the pixel is fill.
+ *   Otherwise scale = nh / Rh, support = 2 max(scale, 1), center = scale (r + 0.5), taps k in [max(0, int(center - support + 0.5)),
+ *   min(nh, int(center + support + 0.5))) with weight cubic((k - center + 0.5) / max(scale, 1)) (Keys' cubic, a = -0.5) divided by their sum; tap k
+ *   reads source row top + k: the filter sees the window [top, top + nh) x [left, left + nw) and nothing else.
+ *   out = round(clamp(sum_y sum_x wy wx pixel, 0, 255)), summed in fp32, ties to even -- the arithmetic of ocn_resized_crop_u8, which is the plan
+ *   (Hs, Ws, top, left, h, w, Ho, Wo, 0, 0); the validation transform is (Hs, Ws, 0, 0, Hs, Ws, Rh, Rw, oy, ox).  With the whole image as the window
+ *   this is torch's F.interpolate(image.float(), (Rh, Rw), mode="bicubic", antialias=True, align_corners=False), windowed, clamped and rounded ONCE.
+ *   It is NOT PIL-compatible: PIL rounds (and clips) an 8-bit intermediate between its two passes, and on whole-image resizes the two differ by
+ *   many levels where the cubic overshoots.
+ *   Refused before any launch: B < 1, Ho or Wo outside [1, 1024], fill outside [0, 255], a null or misaligned operand, arena_bytes not a positive
+ *   multiple of 4.  offsets and plan are never read back, so the kernel makes any content harmless:
+ *     Hs, Ws are forced into [1, 8192], Rh, Rw into [1, 4096], nh into [1, min(4 Rh, 8192)] and nw alike (window anchored at its top-left corner; at
+ *     most 17 taps per axis), top, left into [-32768, 32768], oy, ox into [-4096, 4096];
+ *     every source coordinate is forced into [0, Hs) x [0, Ws) (a window that reaches outside sees the edge pixel repeated);
+ *     the offset is forced into [0, arena_bytes - 4] and down to a multiple of 4, and the address of every byte then read, offset + (y Ws + x) 3 + c,
+ *     into [0, arena_bytes) (an image that runs past the arena's end reads the arena's last byte there).
+ *   Nothing is read outside the arena or written outside out, whatever the two tensors hold.  The host-side builders and check
+ *   (input_pipeline.eval_resample_plan / train_resample_plan / pack_images / check_resample_plan) produce none of these forms. */
+int ocn_resample_u8(const void* arena_u8, int64_t arena_bytes, const int64_t* offsets, const int32_t* plan, int B, void* out_u8, int Ho, int Wo, int fill,
+                    ocn_stream_t stream);
 
 /* ---- device-side colour jitter and grayscale (transform.py:335-364, :442-450: color_jitter(*aug_cfg.color_jitter, p), gray_scale(p)) ----------
  * ocn_color_jitter_u8: img uint8 [B, H, W, 3] (HWC), factors fp32 [B, 4] = (brightness, contrast, saturation, hue) and plan int32 [B] ON THE DEVICE,

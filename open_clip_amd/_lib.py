@@ -36,6 +36,7 @@ SIGNATURES = {
     "ocn_patchify": [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "ocn_patchify_u8": [_p, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "ocn_resized_crop_u8": [_p, _i, _i, _i, _p, _p, _i, _i, _p],
+    "ocn_resample_u8": [_p, _l, _p, _p, _i, _p, _i, _i, _i, _p],
     "ocn_color_jitter_u8": [_p, _i, _i, _i, _p, _p, _p, _p, _p],
     "ocn_embed_assemble_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ocn_embed_assemble_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
@@ -97,7 +98,7 @@ DEBUG_SIGNATURES = {
 _SPECIAL = {"ocn_last_error": ([], ctypes.c_char_p), "ocn_version": ([], _i), "ocn_gemm_tn_det_workspace_bytes": ([_i, _i, _i], _l),
             "ocn_fused_logits_ce_workspace_floats": ([_i, _i], _l), "ocn_gemm_nt_splitk_plan": ([_i, _i, _i], _i), "ocn_layernorm_bwd_det_workspace_floats": ([_i, _i], _l), "ocn_get_tile_rescue": ([], _i)}
 
-ABI_VERSION = 113  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
+ABI_VERSION = 114  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
 
 _lib = None
 _lock = threading.Lock()

@@ -405,6 +405,35 @@ def resized_crop_u8(src, boxes, size, out=None):
     return out
 
 
+def resample_u8(arena, offsets, plan, size, fill=0, out=None):
+    """antialiased bicubic resampling of ragged sources on the device (ocn_resample_u8; defined in include/openclip_hip.h): ``arena`` uint8 [bytes]
+    (a multiple of 4; 16-byte aligned) holds B tightly packed HWC images, ``offsets`` int64 [B] their byte offsets (multiples of 16), ``plan`` int32
+    [B, 10] = (Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox) on the same device, ``size`` an int or (Ho, Wo), ``fill`` the colour 0..255 of output pixels
+    outside the resized image -> uint8 [B, Ho, Wo, 3] (``out`` when given).  The contents of ``offsets`` and ``plan`` are not checked here (they are
+    device data; ``input_pipeline.check_resample_plan`` checks them on the host): the kernel clamps every size, coordinate and address."""
+    Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    if arena.dtype != torch.uint8:
+        raise RuntimeError(f"resample_u8: 'arena' must be uint8 (got {arena.dtype})")
+    if arena.dim() != 1 or arena.numel() == 0 or arena.numel() % 4 != 0:
+        raise RuntimeError(f"resample_u8: 'arena' must be a flat byte buffer [bytes] with bytes a positive multiple of 4 (got {tuple(arena.shape)})")
+    if offsets.dim() != 1 or offsets.numel() == 0:
+        raise RuntimeError(f"resample_u8: 'offsets' must be int64 [B] with B >= 1 (got {tuple(offsets.shape)})")
+    B = offsets.shape[0]
+    if tuple(plan.shape) != (B, 10):
+        raise RuntimeError(f"resample_u8: 'plan' must be int32 [B = {B}, 10] = (Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox) (got {tuple(plan.shape)})")
+    if isinstance(fill, bool) or not isinstance(fill, int) or not 0 <= fill <= 255:
+        raise RuntimeError(f"resample_u8: 'fill' must be an int in [0, 255] (got {fill!r})")
+    ap, op, pp = _chk(arena, torch.uint8, "arena"), _chk(offsets, torch.int64, "offsets"), _chk(plan, torch.int32, "plan")
+    if offsets.device != arena.device or plan.device != arena.device:
+        raise RuntimeError(f"resample_u8: 'offsets' ({offsets.device}), 'plan' ({plan.device}) and 'arena' ({arena.device}) must be on one device")
+    if out is None:
+        out = empty((B, Ho, Wo, 3), torch.uint8, arena)
+    elif tuple(out.shape) != (B, Ho, Wo, 3) or out.device != arena.device:
+        raise RuntimeError(f"resample_u8: 'out' must be uint8 {(B, Ho, Wo, 3)} on {arena.device} (got {tuple(out.shape)} on {out.device})")
+    _lib.call("ocn_resample_u8", ap, arena.numel(), op, pp, B, _chk(out, torch.uint8, "out"), Ho, Wo, fill, _stream())
+    return out
+
+
 def color_jitter_u8(img, factors, plan, out=None):
     """colour jitter + grayscale on the device (ocn_color_jitter_u8; the arithmetic is defined in include/openclip_hip.h): ``img`` uint8 [B, H, W, 3],
     ``factors`` float32 [B, 4] = (brightness, contrast, saturation, hue) and ``plan`` int32 [B] (four 3-bit step codes from the low bits up, bit 12 =

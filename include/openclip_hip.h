@@ -209,31 +209,19 @@ int ocn_attn_pooled_bwd(const void* q, const void* kv, const void* out, const vo
 int ocn_patch_keep_plan(int64_t seed, int B, int G, int K, int32_t* keep, int32_t* inv, ocn_stream_t stream);
 int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int K, ocn_stream_t stream);
 
-/* ---- device-side RandomResizedCrop (transform.py:435-440: RandomResizedCrop(image_size, scale, interpolation=BICUBIC)) ----------------
- * ocn_resized_crop_u8: src uint8 [B, Hs, Ws, 3] (HWC, what ocn_patchify_u8(hwc = 1) reads), boxes int32 [B, 4] = (top, left, height, width) ON THE
- *   DEVICE, out uint8 [B, Ho, Wo, 3].  Crop, then antialiased bicubic resize, rounded once.  Per axis (box side n, output side m):
- *   scale = n / m, support = 2 max(scale, 1), inv = 1 / max(scale, 1); output o: center = scale (o + 0.5), taps k in
- *   [max(0, int(center - support + 0.5)), min(n, int(center + support + 0.5))) with weight cubic((k - center + 0.5) inv) (Keys' cubic, a = -0.5),
- *   divided by their sum; taps are clamped to the crop, not to the source.  out = round(clamp(sum_y sum_x wy wx pixel, 0, 255)), summed in fp32,
- *   ties to even: F.interpolate(crop.float(), (Ho, Wo), mode="bicubic", antialias=True, align_corners=False), clamped and rounded.  It is NOT
- *   bit-compatible with PIL's fixed-point resampler (8-bit intermediate): the two differ by at most one level on roughly a sixth of noise values.
- *   1 <= Ho, Wo <= 1024 and 1 <= Hs, Ws <= 8192, refused before any launch.  The boxes are never read back, so the kernel makes a bad one harmless:
- *   a side is forced into [1, 4 * output side] (box anchored at its top-left corner; at most 17 taps per axis) and every source coordinate into the
- *   image (a box that reaches outside reads the edge pixel repeated) -- no access leaves src whatever boxes holds.  The host-side builders
- *   (input_pipeline.random_resized_crop_boxes / check_boxes) never produce either form. */
-int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
-
-/* ---- device-side resampling of ragged sources: the train crop and the validation transform in one form -------------------------------------
- * (transform.py:435-440 RandomResizedCrop; :461-492 image_transform(is_train=False): Resize / ResizeKeepRatio + CenterCrop / CenterCropOrPad)
- * ocn_resample_u8: arena uint8 [arena_bytes], one device buffer (base 16-byte aligned, arena_bytes a positive multiple of 4); offsets int64 [B] ON THE
- *   DEVICE = the byte offset of image b in the arena, a multiple of 16; image b is HWC uint8, tightly packed, Hs * Ws * 3 bytes; plan int32 [B, 10]
- *   ON THE DEVICE = (Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox); out uint8 [B, Ho, Wo, 3]; fill in [0, 255], written to all three channels.
+/* ---- device-side resampling: the train crop and the validation transform in one form ----------------------------------------------------
+ * (transform.py:435-440 RandomResizedCrop(image_size, scale, interpolation=BICUBIC); :461-492 image_transform(is_train=False): Resize /
+ * ResizeKeepRatio + CenterCrop / CenterCropOrPad).  One tile routine (csrc/resample.hip) behind two entry points.
+ * ocn_resample_u8: RAGGED sources.  arena uint8 [arena_bytes], one device buffer (base 16-byte aligned, arena_bytes a positive multiple of 4);
+ *   offsets int64 [B] ON THE DEVICE = the byte offset of image b in the arena, a multiple of 16; image b is HWC uint8, tightly packed, Hs * Ws * 3
+ *   bytes; plan int32 [B, 10] ON THE DEVICE = (Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox); out uint8 [B, Ho, Wo, 3]; fill in [0, 255], written to all
+ *   three channels.
  *   Per axis (y shown, x alike): output row o is row r = o + oy of the image virtually resized to Rh rows; r < 0 or r >= Rh: the pixel is fill.
  *   Otherwise scale = nh / Rh, support = 2 max(scale, 1), center = scale (r + 0.5), taps k in [max(0, int(center - support + 0.5)),
  *   min(nh, int(center + support + 0.5))) with weight cubic((k - center + 0.5) / max(scale, 1)) (Keys' cubic, a = -0.5) divided by their sum; tap k
  *   reads source row top + k: the filter sees the window [top, top + nh) x [left, left + nw) and nothing else.
- *   out = round(clamp(sum_y sum_x wy wx pixel, 0, 255)), summed in fp32, ties to even -- the arithmetic of ocn_resized_crop_u8, which is the plan
- *   (Hs, Ws, top, left, h, w, Ho, Wo, 0, 0); the validation transform is (Hs, Ws, 0, 0, Hs, Ws, Rh, Rw, oy, ox).  With the whole image as the window
+ *   out = round(clamp(sum_y sum_x wy wx pixel, 0, 255)), summed in fp32, ties to even.  The train crop is the plan
+ *   (Hs, Ws, top, left, h, w, Ho, Wo, 0, 0), the validation transform (Hs, Ws, 0, 0, Hs, Ws, Rh, Rw, oy, ox).  With the whole image as the window
  *   this is torch's F.interpolate(image.float(), (Rh, Rw), mode="bicubic", antialias=True, align_corners=False), windowed, clamped and rounded ONCE.
  *   It is NOT PIL-compatible: PIL rounds (and clips) an 8-bit intermediate between its two passes, and on whole-image resizes the two differ by
  *   many levels where the cubic overshoots.
@@ -245,7 +233,18 @@ int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t
  *     the offset is forced into [0, arena_bytes - 4] and down to a multiple of 4, and the address of every byte then read, offset + (y Ws + x) 3 + c,
  *     into [0, arena_bytes) (an image that runs past the arena's end reads the arena's last byte there).
  *   Nothing is read outside the arena or written outside out, whatever the two tensors hold.  The host-side builders and check
- *   (input_pipeline.eval_resample_plan / train_resample_plan / pack_images / check_resample_plan) produce none of these forms. */
+ *   (input_pipeline.eval_resample_plan / train_resample_plan / pack_images / check_resample_plan) produce none of these forms.
+ * ocn_resized_crop_u8: sources of ONE size.  src uint8 [B, Hs, Ws, 3] (HWC, what ocn_patchify_u8(hwc = 1) reads; any byte alignment), boxes int32
+ *   [B, 4] = (top, left, height, width) ON THE DEVICE, out uint8 [B, Ho, Wo, 3]: the arithmetic above on the plan
+ *   (Hs, Ws, top, left, height, width, Ho, Wo, 0, 0) of every image -- crop, then antialiased bicubic resize, rounded once; the taps are clamped to the
+ *   crop, not to the source, and no pixel is fill: F.interpolate(crop.float(), (Ho, Wo), mode="bicubic", antialias=True, align_corners=False), clamped
+ *   and rounded.  It is NOT bit-compatible with PIL's fixed-point resampler (8-bit intermediate): the two differ by at most one level on roughly a
+ *   sixth of noise values.
+ *   1 <= Ho, Wo <= 1024 and 1 <= Hs, Ws <= 8192, refused before any launch.  The boxes are never read back, so the kernel makes a bad one harmless:
+ *   a side is forced into [1, 4 * output side] (box anchored at its top-left corner; at most 17 taps per axis) and every source coordinate into the
+ *   image (a box that reaches outside reads the edge pixel repeated) -- no access leaves src whatever boxes holds.  The host-side builders
+ *   (input_pipeline.random_resized_crop_boxes / check_boxes) never produce either form. */
+int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
 int ocn_resample_u8(const void* arena_u8, int64_t arena_bytes, const int64_t* offsets, const int32_t* plan, int B, void* out_u8, int Ho, int Wo, int fill,
                     ocn_stream_t stream);
 

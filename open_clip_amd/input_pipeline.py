@@ -57,60 +57,68 @@ from . import ops
 MAX_CROP_RATIO = 4  # largest box side / output side ocn_resized_crop_u8 resamples as given (17 taps per axis); the kernel clamps a larger side
 
 
+def _size2(size):
+    return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+
+
+def _sample_crop_boxes(Hs, Ws, scale, ratio, generator):
+    """the one sampler behind ``random_resized_crop_boxes`` and ``train_resample_plan``: ``Hs``, ``Ws`` int64 [B], the size of each image -> int64
+    [B, 4] = (top, left, height, width), by the rule stated at ``random_resized_crop_boxes`` with every image judged against its own size"""
+    B = Hs.shape[0]
+    u = torch.rand((4, B, 10), dtype=torch.float64, generator=generator)
+    target = (Hs * Ws).double()[:, None] * (scale[0] + (scale[1] - scale[0]) * u[0])
+    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
+    r = torch.exp(lr0 + (lr1 - lr0) * u[1])
+    w = torch.round(torch.sqrt(target * r)).long()
+    h = torch.round(torch.sqrt(target / r)).long()
+    ok = (w > 0) & (w <= Ws[:, None]) & (h > 0) & (h <= Hs[:, None])
+    first = ok.int().argmax(dim=1, keepdim=True)  # the first maximum: the first attempt that fits
+    w, h, found = w.gather(1, first)[:, 0], h.gather(1, first)[:, 0], ok.any(dim=1)
+    top = torch.floor(u[2, :, 0] * (Hs - h + 1).clamp(min=1)).long()
+    left = torch.floor(u[3, :, 0] * (Ws - w + 1).clamp(min=1)).long()
+    in_ratio = Ws.double() / Hs.double()  # the fallback, per image (torch.round is Python's round: half to even)
+    narrow, wide = in_ratio < min(ratio), in_ratio > max(ratio)
+    fh = torch.where(narrow, torch.minimum(Hs, torch.round(Ws.double() / min(ratio)).long()), Hs)
+    fw = torch.where(wide & ~narrow, torch.minimum(Ws, torch.round(Hs.double() * max(ratio)).long()), Ws)
+    return torch.where(found[:, None], torch.stack([top, left, h, w], dim=1), torch.stack([(Hs - fh) // 2, (Ws - fw) // 2, fh, fw], dim=1))
+
+
 def random_resized_crop_boxes(B, Hs, Ws, scale=(0.9, 1.0), ratio=(3 / 4, 4 / 3), generator=None):
     """The sampling rule of torchvision's ``RandomResizedCrop.get_params`` for B images of one source size, vectorised in torch on the CPU:
     host int32 [B, 4] = (top, left, height, width).  Up to 10 attempts per image, each an area ``Hs * Ws * U(scale)`` and an aspect ratio
     log-uniform in ``ratio`` with ``w = round(sqrt(area * r))``, ``h = round(sqrt(area / r))``; the first attempt with ``0 < w <= Ws`` and
     ``0 < h <= Hs`` wins and the corner is uniform in the room left; an image without one gets the centre crop with the source's ratio clamped
     into ``ratio``.  Reproducible under ``generator``; it does NOT reproduce torchvision's random stream (other draws, other order)."""
-    area = float(Hs * Ws)
-    u = torch.rand((4, B, 10), dtype=torch.float64, generator=generator)
-    target = area * (scale[0] + (scale[1] - scale[0]) * u[0])
-    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
-    r = torch.exp(lr0 + (lr1 - lr0) * u[1])
-    w = torch.round(torch.sqrt(target * r)).long()
-    h = torch.round(torch.sqrt(target / r)).long()
-    ok = (w > 0) & (w <= Ws) & (h > 0) & (h <= Hs)
-    first = ok.int().argmax(dim=1, keepdim=True)  # the first maximum: the first attempt that fits
-    w, h, found = w.gather(1, first)[:, 0], h.gather(1, first)[:, 0], ok.any(dim=1)
-    top = torch.floor(u[2, :, 0] * (Hs - h + 1).clamp(min=1)).long()
-    left = torch.floor(u[3, :, 0] * (Ws - w + 1).clamp(min=1)).long()
-    in_ratio = Ws / Hs  # the fallback: one box for every image that found none
-    if in_ratio < min(ratio):
-        fw, fh = Ws, min(Hs, int(round(Ws / min(ratio))))
-    elif in_ratio > max(ratio):
-        fh, fw = Hs, min(Ws, int(round(Hs * max(ratio))))
-    else:
-        fw, fh = Ws, Hs
-    fallback = torch.tensor([(Hs - fh) // 2, (Ws - fw) // 2, fh, fw])
-    return torch.where(found[:, None], torch.stack([top, left, h, w], dim=1), fallback[None, :]).to(torch.int32)
+    return _sample_crop_boxes(torch.full((B,), Hs, dtype=torch.int64), torch.full((B,), Ws, dtype=torch.int64), scale, ratio, generator).to(torch.int32)
+
+
+def _raise_first(bads, prefix, describe):
+    """``bads``: (bool [B], text) pairs in the order of the checks.  The first pair with a true entry raises ValueError for its first such image i:
+    ``prefix`` + ``describe(i)`` + the pair's text"""
+    for bad, what in bads:
+        if bool(bad.any()):
+            raise ValueError(f"{prefix}{describe(int(bad.int().argmax()))} {what}")
 
 
 def check_boxes(boxes, Hs, Ws, size):
     """host-side check of crop boxes [B, 4] = (top, left, height, width) against the source size and the output ``size`` (int or (Ho, Wo)):
     ValueError for an empty box, one that leaves the source, or a side of more than ``MAX_CROP_RATIO`` x the output side"""
-    Ho, Wo = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    Ho, Wo = _size2(size)
     if boxes.is_cuda:
         raise ValueError("check_boxes: a host-side check (the boxes of a device tensor are never read back)")
     if boxes.dim() != 2 or boxes.shape[1] != 4 or boxes.is_floating_point():
         raise ValueError(f"check_boxes: expected integer boxes [B, 4] = (top, left, height, width), got {boxes.dtype} {tuple(boxes.shape)}")
     b = boxes.long()
     top, left, h, w = b[:, 0], b[:, 1], b[:, 2], b[:, 3]
-    for bad, what in (((h <= 0) | (w <= 0), "is empty"),
-                      ((top < 0) | (left < 0) | (top + h > Hs) | (left + w > Ws), f"lies outside the {Hs} x {Ws} source"),
-                      ((h > MAX_CROP_RATIO * Ho) | (w > MAX_CROP_RATIO * Wo), f"has a side of more than {MAX_CROP_RATIO} x the {Ho} x {Wo} output")):
-        if bool(bad.any()):
-            i = int(bad.int().argmax())
-            raise ValueError(f"check_boxes: box {i} = {tuple(b[i].tolist())} (top, left, height, width) {what}")
+    _raise_first((((h <= 0) | (w <= 0), "is empty"),
+                  ((top < 0) | (left < 0) | (top + h > Hs) | (left + w > Ws), f"lies outside the {Hs} x {Ws} source"),
+                  ((h > MAX_CROP_RATIO * Ho) | (w > MAX_CROP_RATIO * Wo), f"has a side of more than {MAX_CROP_RATIO} x the {Ho} x {Wo} output")),
+                 "check_boxes: box ", lambda i: f"{i} = {tuple(b[i].tolist())} (top, left, height, width)")
 
 
 RESAMPLE_MAX_SOURCE, RESAMPLE_MAX_RESIZED = 8192, 4096  # the ranges ocn_resample_u8 forces a plan's source sides and resized sides into
 RESAMPLE_ALIGN = 16  # byte alignment of an image inside the arena
 RESIZE_MODES = ("shortest", "longest", "squash")
-
-
-def _size2(size):
-    return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
 
 
 def _sizes(sizes):
@@ -163,25 +171,8 @@ def train_resample_plan(sizes, image_size, scale=(0.9, 1.0), ratio=(3 / 4, 4 / 3
     ``ratio``.  The draws are those of ``random_resized_crop_boxes``: for sources of one size the two give the same boxes under the same generator."""
     Ho, Wo = _size2(image_size)
     s = _sizes(sizes)
-    B, Hs, Ws = s.shape[0], s[:, 0], s[:, 1]
-    u = torch.rand((4, B, 10), dtype=torch.float64, generator=generator)
-    target = (Hs * Ws).double()[:, None] * (scale[0] + (scale[1] - scale[0]) * u[0])
-    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
-    r = torch.exp(lr0 + (lr1 - lr0) * u[1])
-    w = torch.round(torch.sqrt(target * r)).long()
-    h = torch.round(torch.sqrt(target / r)).long()
-    ok = (w > 0) & (w <= Ws[:, None]) & (h > 0) & (h <= Hs[:, None])
-    first = ok.int().argmax(dim=1, keepdim=True)  # the first maximum: the first attempt that fits
-    w, h, found = w.gather(1, first)[:, 0], h.gather(1, first)[:, 0], ok.any(dim=1)
-    top = torch.floor(u[2, :, 0] * (Hs - h + 1).clamp(min=1)).long()
-    left = torch.floor(u[3, :, 0] * (Ws - w + 1).clamp(min=1)).long()
-    in_ratio = Ws.double() / Hs.double()  # the fallback, per image
-    narrow, wide = in_ratio < min(ratio), in_ratio > max(ratio)
-    fh = torch.where(narrow, torch.minimum(Hs, torch.round(Ws.double() / min(ratio)).long()), Hs)
-    fw = torch.where(wide & ~narrow, torch.minimum(Ws, torch.round(Hs.double() * max(ratio)).long()), Ws)
-    box = torch.where(found[:, None], torch.stack([top, left, h, w], dim=1), torch.stack([(Hs - fh) // 2, (Ws - fw) // 2, fh, fw], dim=1))
-    tail = torch.tensor([Ho, Wo, 0, 0]).expand(B, 4)
-    return torch.cat([s, box, tail], dim=1).to(torch.int32)
+    box = _sample_crop_boxes(s[:, 0], s[:, 1], scale, ratio, generator)
+    return torch.cat([s, box, torch.tensor([Ho, Wo, 0, 0]).expand(s.shape[0], 4)], dim=1).to(torch.int32)
 
 
 def pack_images(images, arena, offsets_out):
@@ -222,18 +213,16 @@ def check_resample_plan(plan, offsets, arena_bytes, size):
     p, off = plan.long(), offsets.long()
     Hs, Ws, top, left, nh, nw, Rh, Rw, oy, ox = (p[:, i] for i in range(10))
     K, S, R = MAX_CROP_RATIO, RESAMPLE_MAX_SOURCE, RESAMPLE_MAX_RESIZED
-    for bad, what in (((Hs < 1) | (Ws < 1) | (Hs > S) | (Ws > S), f"has a source side outside [1, {S}]"),
-                      ((nh <= 0) | (nw <= 0), "has an empty window"),
-                      ((top < 0) | (left < 0) | (top + nh > Hs) | (left + nw > Ws), "has a window that lies outside its source"),
-                      ((Rh < 1) | (Rw < 1) | (Rh > R) | (Rw > R), f"has a resized side outside [1, {R}]"),
-                      ((nh > K * Rh) | (nw > K * Rw), f"has a window side of more than {K} x its resized side: the loader must reduce such an image first "
-                                                      "(for instance with PIL's Image.draft at decode time)"),
-                      ((oy.abs() > R) | (ox.abs() > R), f"has an output offset beyond {R}"),
-                      ((off < 0) | (off % RESAMPLE_ALIGN != 0), f"has an offset that is negative or no multiple of {RESAMPLE_ALIGN}"),
-                      (off + Hs * Ws * 3 > int(arena_bytes), f"does not fit the arena of {int(arena_bytes)} bytes")):
-        if bool(bad.any()):
-            i = int(bad.int().argmax())
-            raise ValueError(f"check_resample_plan: image {i} (plan {tuple(p[i].tolist())}, offset {int(off[i])}) {what}")
+    _raise_first((((Hs < 1) | (Ws < 1) | (Hs > S) | (Ws > S), f"has a source side outside [1, {S}]"),
+                  ((nh <= 0) | (nw <= 0), "has an empty window"),
+                  ((top < 0) | (left < 0) | (top + nh > Hs) | (left + nw > Ws), "has a window that lies outside its source"),
+                  ((Rh < 1) | (Rw < 1) | (Rh > R) | (Rw > R), f"has a resized side outside [1, {R}]"),
+                  ((nh > K * Rh) | (nw > K * Rw), f"has a window side of more than {K} x its resized side: the loader must reduce such an image first "
+                                                  "(for instance with PIL's Image.draft at decode time)"),
+                  ((oy.abs() > R) | (ox.abs() > R), f"has an output offset beyond {R}"),
+                  ((off < 0) | (off % RESAMPLE_ALIGN != 0), f"has an offset that is negative or no multiple of {RESAMPLE_ALIGN}"),
+                  (off + Hs * Ws * 3 > int(arena_bytes), f"does not fit the arena of {int(arena_bytes)} bytes")),
+                 "check_resample_plan: image ", lambda i: f"{i} (plan {tuple(p[i].tolist())}, offset {int(off[i])})")
 
 
 JITTER_STEPS = ("brightness", "contrast", "saturation", "hue")  # step code k + 1 in a plan entry, column k of factors
@@ -309,15 +298,13 @@ def check_jitter(factors, plan):
     twice = torch.zeros(plan.shape[0], dtype=torch.bool)
     for c in range(1, 5):
         twice |= (codes == c).sum(dim=1) > 1
-    for bad, what in ((~torch.isfinite(factors).all(dim=1), "has a factor that is not finite"),
-                      ((factors[:, :3] < 0).any(dim=1), "has a negative brightness, contrast or saturation factor"),
-                      (factors[:, 3].abs() > 0.5, "has a hue shift outside [-0.5, 0.5]"),
-                      ((codes > 4).any(dim=1), "has a step code above 4"),
-                      (twice, "has a step twice"),
-                      ((p < 0) | (p >= 2 * JITTER_GRAY_BIT), "has bits above the grayscale bit")):
-        if bool(bad.any()):
-            i = int(bad.int().argmax())
-            raise ValueError(f"check_jitter: image {i} (factors {tuple(factors[i].tolist())}, plan {int(p[i]):#x}) {what}")
+    _raise_first(((~torch.isfinite(factors).all(dim=1), "has a factor that is not finite"),
+                  ((factors[:, :3] < 0).any(dim=1), "has a negative brightness, contrast or saturation factor"),
+                  (factors[:, 3].abs() > 0.5, "has a hue shift outside [-0.5, 0.5]"),
+                  ((codes > 4).any(dim=1), "has a step code above 4"),
+                  (twice, "has a step twice"),
+                  ((p < 0) | (p >= 2 * JITTER_GRAY_BIT), "has bits above the grayscale bit")),
+                 "check_jitter: image ", lambda i: f"{i} (factors {tuple(factors[i].tolist())}, plan {int(p[i]):#x})")
 
 
 class HostTextPlan:
@@ -486,17 +473,21 @@ class DeviceBatchPipeline:
         if self.ragged_cfg is not None:
             raise RuntimeError("DeviceBatchPipeline: a ragged pipeline packs its arena in submit(images, text_host); it has no image staging buffer")
         s = self.slots[self._w]
-        if s["host_done"] is not None and not s["host_done"].query():
-            s["host_done"].synchronize()  # the previous transfer out of this pinned buffer has finished
+        self._wait_host(s)
         return s["h_image"], s["h_text"]
+
+    @staticmethod
+    def _wait_host(s):
+        """before the host writes any pinned buffer of slot ``s``: the slot's PREVIOUS transfer (``depth`` batches ago) may still read it -- rare"""
+        if s["host_done"] is not None and not s["host_done"].query():
+            s["host_done"].synchronize()
 
     def _submit_ragged(self, s, images, text_host, sizes, plan):
         """the host side of a ragged batch: pack, plan, check -- everything that can refuse the batch, before anything is enqueued"""
         cfg, B = self.ragged_cfg, s["offsets"].shape[0]
         if images is None or text_host is None or torch.is_tensor(images) and images.dim() != 4 or len(images) != B:
             raise ValueError(f"DeviceBatchPipeline: a ragged submit takes B = {B} images (uint8 [Hs, Ws, 3] each) and their text")
-        if s["host_done"] is not None and not s["host_done"].query():
-            s["host_done"].synchronize()  # the slot's previous transfer still reads the pinned arena
+        self._wait_host(s)
         used = pack_images(images, s["h_arena"], s["h_offsets"])
         packed = torch.tensor([tuple(torch.as_tensor(im).shape[:2]) for im in images])
         if sizes is not None and not torch.equal(_sizes(sizes), packed):
@@ -559,19 +550,16 @@ class DeviceBatchPipeline:
                 ht.copy_(text_host)
         plan = None
         if self.plan_text_vocab is not None:
-            if s["host_done"] is not None and not s["host_done"].query():
-                s["host_done"].synchronize()  # the slot's PREVIOUS transfer (``depth`` batches ago) still reads the pinned plan buffers: rare
+            self._wait_host(s)
             plan = HostTextPlan(src_t, self.plan_text_vocab, self.attn_buckets)
             s["h_plan_ints"][:plan.ints.numel()].copy_(plan.ints)
             s["h_plan_tokens"][:plan.M].copy_(plan.tokens)
         s["plan"] = plan
         if self.crop_size is not None:
-            if s["host_done"] is not None and not s["host_done"].query():
-                s["host_done"].synchronize()  # as for the plan: the slot's previous transfer may still read the pinned boxes
+            self._wait_host(s)
             s["h_boxes"].copy_(boxes)
         if self.jitter:
-            if s["host_done"] is not None and not s["host_done"].query():
-                s["host_done"].synchronize()  # as for the boxes
+            self._wait_host(s)
             s["h_jit_factors"].copy_(jitter[0])
             s["h_jit_plan"].copy_(jitter[1])
         with torch.cuda.stream(self.copy_stream):

@@ -2,7 +2,12 @@
 length R of the virtually resized axis and the slice of it that is the output; pixels outside the resized image are the fill colour.  The axis
 weights, the acceptance rule (DELTA = 2**-9, at most 2 % of the oracle's values in the band, asserted on the oracle alone) and their derivation are
 those of tests/resized_crop_util.py: the arithmetic is the same, tap for tap.  tests/test_resample.py checks this oracle against
-``F.interpolate(..., mode="bicubic", antialias=True)`` in float64 before it judges anything."""
+``F.interpolate(..., mode="bicubic", antialias=True)`` in float64 before it judges anything.
+
+``golden_cases()`` are the inputs whose outputs tests/golden/resample_parent.npz records, once, from the library of the commit BEFORE the two kernels
+became one routine (tools/resample_golden.py writes the file): the new library must give the same bytes."""
+import os
+
 import numpy as np
 
 from tests.resized_crop_util import DELTA, MAX_BAND_FRACTION, MAX_RATIO, assert_matches, axis_matrix, cubic  # noqa: F401  (re-exported)
@@ -82,3 +87,81 @@ def oracle_clamped(arena, offsets, plan, size, fill=0):
         addr = off + (rows[:, None, None] * Ws + cols[None, :, None]) * 3 + np.arange(3)[None, None, :]
         out.append(oracle_window(arena[np.clip(addr, 0, arena.size - 1)], Rh, Rw, oy, ox, size, fill))
     return np.stack(out)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "resample_parent.npz")
+SIX_BOXES = [(2, 2, 16, 16), (0, 0, 40, 52), (3, 5, 31, 37), (1, 7, 9, 11), (24, 36, 16, 16), (7, 9, 1, 1)]
+
+
+def last_in_the_arena_case():
+    """two noise images, the second with rows of 132 bytes (every row starts on a dword), flush with the arena's end, and a tile column of it whose
+    span starts at byte 9 of a row: ragged + aligned rows + a span shifted by 1 + the arena-end clamp -> (arena, offsets, plan, size)"""
+    rng = np.random.default_rng(31)
+    images = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for h, w in ((31, 29), (20, 44))]
+    arena, offsets = pack(images)
+    assert arena.size == 5344 and offsets.tolist() == [0, 2704] and offsets[1] + 20 * 132 == arena.size
+    plan = np.asarray([(31, 29, 2, 1, 27, 26, 17, 33, 0, 0), (20, 44, 1, 3, 19, 41, 17, 33, 0, 0)], dtype=np.int32)
+    return arena, offsets, plan, (17, 33)
+
+
+def golden_cases():
+    """the inputs of the existing GPU tests, rebuilt from their seeds as numpy arrays: a list of dicts with 'name', 'size' and either 'src' uint8
+    [B, Hs, Ws, 3], 'boxes' int32 [B, 4] and 'shift' (the bytes src starts into its allocation) for ``ops.resized_crop_u8``, or 'arena', 'offsets',
+    'plan' and 'fill' for ``ops.resample_u8``"""
+    import torch
+    from open_clip_amd.input_pipeline import eval_resample_plan, train_resample_plan
+
+    def crop(name, shape, seed, boxes, size, shift=0):
+        src = np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8)
+        return {"name": name, "src": src, "boxes": np.asarray(boxes, dtype=np.int32), "size": size, "shift": shift}
+
+    def ragged(name, arena, offsets, plan, size, fill):
+        return {"name": name, "arena": arena, "offsets": np.asarray(offsets, dtype=np.int64), "plan": np.asarray(plan, dtype=np.int32), "size": size, "fill": fill}
+
+    cases = [crop("crop_six_boxes", (6, 40, 52, 3), 1, SIX_BOXES, 16),
+             crop("crop_70x70_to_23x16", (2, 70, 70, 3), 2, [(3, 5, 64, 64), (6, 0, 64, 64)], (23, 16)),
+             crop("crop_tile_edge_17x33", (2, 40, 52, 3), 3, [(0, 0, 40, 52), (5, 4, 30, 41)], (17, 33)),
+             crop("crop_bad_boxes", (3, 40, 52, 3), 6, [(-5, -4, 20, 24), (2, 1, 30, 45), (20, 30, 28, 25)], (12, 8)),
+             crop("crop_src_one_byte_in", (2, 40, 52, 3), 7, [(0, 0, 40, 52), (3, 5, 31, 37)], (16, 20), shift=1)]
+    sizes = torch.tensor(SIZES)
+    arena, offsets = pack(noise_images(1234))
+    for mode in ("shortest", "longest", "squash"):
+        cases.append(ragged(f"ragged_eval_{mode}_to_32", arena, offsets, eval_resample_plan(sizes, 32, mode).numpy(), 32, 7))
+    plan = train_resample_plan(sizes, 32, scale=(0.3, 1.0), generator=torch.Generator().manual_seed(2)).numpy().copy()
+    for b, box in {0: (3, 5, 32, 32), 1: (7, 9, 1, 1), 2: (37 - 32, 121 - 32, 32, 32), 3: (128 - 56, 40 - 36, 56, 36), 4: (1, 7, 9, 11)}.items():
+        plan[b, 2:6] = box
+    cases.append(ragged("ragged_train_plans", arena, offsets, plan, 32, 0))
+    plan, offs = bad_plans(offsets)
+    cases.append(ragged("ragged_bad_plans", arena, offs, plan, 32, 7))
+    a2, o2, p2, size = last_in_the_arena_case()
+    cases.append(ragged("ragged_aligned_rows_last_in_the_arena", a2, o2, p2, size, 0))
+    return cases
+
+
+def bad_plans(offsets):
+    """plans and offsets of the twelve SIZES images that the host-side check refuses (five of them) -> (plan int32 [12, 10], offsets int64 [12])"""
+    import torch
+    from open_clip_amd.input_pipeline import eval_resample_plan
+    plan = eval_resample_plan(torch.tensor(SIZES), 32, "shortest").numpy().copy()
+    offs = np.asarray(offsets).copy()
+    plan[0, 2] = -3                                    # top = -3: the first row repeated (image 0 lies first: above it is the sentinel)
+    plan[11, 0] += 2; plan[11, 4] += 2                 # noqa: E702  Hs two rows more than stored, in the LAST image: its end runs past the arena
+    plan[5, 0] += 2; plan[5, 4] += 2                   # noqa: E702  ... and in one in the middle: the two rows are the next image's first bytes
+    offs[10] = offsets[11] + 4096                      # an offset 4096 bytes past the last image: beyond the arena's end
+    plan[6, 6] = 0                                     # R = 0: resampled as R = 1
+    plan[7, 4] = 5 * plan[7, 6]                        # n = 5 R: resampled as n = 4 R (the rows below the source: its last row repeated)
+    return plan, offs
+
+
+def run_golden_case(case, dev):
+    """one case of ``golden_cases()`` through ``ops`` on device ``dev`` -> uint8 numpy [B, Ho, Wo, 3]"""
+    import torch
+    from open_clip_amd import ops
+    if "src" in case:
+        src = torch.from_numpy(case["src"])
+        buf = torch.zeros(src.numel() + case["shift"], dtype=torch.uint8, device=dev)
+        view = buf[case["shift"]:].view(src.shape)
+        view.copy_(src)
+        return ops.resized_crop_u8(view, torch.from_numpy(case["boxes"]).to(dev), case["size"]).cpu().numpy()
+    return ops.resample_u8(torch.from_numpy(case["arena"]).to(dev), torch.from_numpy(case["offsets"]).to(dev), torch.from_numpy(case["plan"]).to(dev),
+                           case["size"], fill=case["fill"]).cpu().numpy()

@@ -155,6 +155,18 @@ def test_train_plan_fallback_is_each_images_own_clamped_centre_crop():
     assert plan[:, 2:6].tolist() == [[0, 0, 10, 12], [0, 0, 30, 27]]
 
 
+def test_train_plan_and_box_sampler_agree_on_the_fallback():
+    """scale = (4, 4): no attempt fits, every image takes the fallback -- narrow, wide and in range, the by-hand centre crops of
+    tests/test_resized_crop.py (round(40 * 4 / 3) = 53 of the 200 rows, round(40 / (3 / 4)) = 53 of the 200 columns), from both entries of the one sampler"""
+    by_hand = {(40, 200): [0, 73, 40, 53], (200, 40): [73, 0, 53, 40], (64, 64): [0, 0, 64, 64]}
+    for (Hs, Ws), box in by_hand.items():
+        boxes = random_resized_crop_boxes(3, Hs, Ws, scale=(4.0, 4.0), generator=torch.Generator().manual_seed(13))
+        plan = train_resample_plan(torch.tensor([(Hs, Ws)] * 3), 32, scale=(4.0, 4.0), generator=torch.Generator().manual_seed(13))
+        assert boxes.dtype == torch.int32 and boxes.tolist() == [box] * 3 and torch.equal(plan[:, 2:6], boxes)
+    mixed = train_resample_plan(torch.tensor(list(by_hand)), 32, scale=(4.0, 4.0), generator=torch.Generator().manual_seed(13))
+    assert mixed[:, 2:6].tolist() == list(by_hand.values())
+
+
 GOOD = [40, 52, 2, 3, 32, 32, 8, 8, 0, 0]
 
 

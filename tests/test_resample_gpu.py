@@ -112,7 +112,9 @@ def test_train_plans_on_the_ragged_set(dev, ragged):
 
 
 def test_fixed_size_sources_match_the_crop_kernel_bit_for_bit(dev):
-    """on sources of one size with dword-aligned rows, a train plan is a box: ocn_resample_u8 and ocn_resized_crop_u8 do the same arithmetic"""
+    """on sources of one size with dword-aligned rows, a train plan is a box: ocn_resample_u8 and ocn_resized_crop_u8 do the same arithmetic.  Both
+    are now csrc/resample.hip's resample_tile, so this compares a routine with itself (the two kernels still fill their descriptions and choose
+    their load modes separately); what holds the arithmetic to that of the two kernels it came from is test_outputs_are_the_bytes_of_the_parent_commit"""
     src = torch.from_numpy(np.random.default_rng(9).integers(0, 256, (4, 64, 64, 3), dtype=np.uint8))
     plan = train_resample_plan(torch.tensor([(64, 64)] * 4), 48, scale=(0.5, 1.0), generator=torch.Generator().manual_seed(4))
     offsets = torch.arange(4, dtype=torch.int64) * (64 * 64 * 3)
@@ -139,14 +141,7 @@ def test_bad_plans_give_the_documented_clamped_result(dev, ragged):
     images, arena, offsets = ragged
     G = 1 << 20
     size = 32
-    plan = eval_resample_plan(SIZES_T, size, "shortest").numpy().copy()
-    offs = offsets.copy()
-    plan[0, 2] = -3                                    # top = -3: the first row repeated (image 0 lies first: above it is the sentinel)
-    plan[11, 0] += 2; plan[11, 4] += 2                 # noqa: E702  Hs two rows more than stored, in the LAST image: its end runs past the arena
-    plan[5, 0] += 2; plan[5, 4] += 2                   # noqa: E702  ... and in one in the middle: the two rows are the next image's first bytes
-    offs[10] = offsets[11] + 4096                      # an offset 4096 bytes past the last image: beyond the arena's end
-    plan[6, 6] = 0                                     # R = 0: resampled as R = 1
-    plan[7, 4] = 5 * plan[7, 6]                        # n = 5 R: resampled as n = 4 R (the rows below the source: its last row repeated)
+    plan, offs = U.bad_plans(offsets)  # top = -3; two rows too many in the last image and in one in the middle; an offset beyond the arena; R = 0; n = 5 R
     bad = 0
     for b in range(len(U.SIZES)):  # five are refused by the host-side check (image 5's plan is consistent in itself: only the packer knows better)
         try:
@@ -164,6 +159,40 @@ def test_bad_plans_give_the_documented_clamped_result(dev, ragged):
         assert bool((big[:G] == sentinel).all()) and bool((big[G + arena.size:] == sentinel).all())
     assert np.array_equal(outs[0], outs[1])
     _judge(outs[0], ref, plan, "bad plans")
+
+
+def test_aligned_rows_last_in_the_arena(dev):
+    """ragged + dword-aligned rows + a span that starts at byte 9 of a row (shifted down by 1) + the arena-end clamp: one dword per tap where the
+    kernel used to take the aligned pair.  Two tile rows and two tile columns per image; the second image ends with the arena, which lies between
+    1 MiB of a sentinel byte on each side, so a dword read past its end would change the output with the sentinel"""
+    arena, offsets, plan, size = U.last_in_the_arena_case()
+    assert plan[1, 3] * 3 == 9 and (plan[1, 1] * 3) % 4 == 0 and offsets[1] % 4 == 0
+    check_resample_plan(torch.from_numpy(plan), torch.from_numpy(offsets), arena.size, size)
+    ref = U.oracle(arena, offsets, plan, size)
+    G, outs = 1 << 20, []
+    for sentinel in (0x5A, 0xA5):
+        big = torch.full((G + arena.size + G,), sentinel, dtype=torch.uint8, device=dev)
+        inner = big[G:G + arena.size]
+        inner.copy_(torch.from_numpy(arena))
+        outs.append(ops.resample_u8(inner, torch.from_numpy(offsets).to(dev), torch.from_numpy(plan).to(dev), size).cpu().numpy())
+        assert bool((big[:G] == sentinel).all()) and bool((big[G + arena.size:] == sentinel).all())
+    assert np.array_equal(outs[0], outs[1])
+    for b in range(2):
+        U.assert_matches(outs[0][b], ref[b], f"last in the arena, image {b} plan {tuple(int(v) for v in plan[b])}")
+
+
+def test_outputs_are_the_bytes_of_the_parent_commit(dev):
+    """tests/golden/resample_parent.npz: what the two separate kernels (csrc/resized_crop.hip and csrc/resample.hip of the commit before they became
+    one tile routine) wrote for ``U.golden_cases()`` -- the inputs of this file's and tests/test_resized_crop_gpu.py's tests.  Every byte must still
+    be the same: the same taps, the same weights, the same order of summation, whichever load mode brings the bytes in"""
+    golden = np.load(U.GOLDEN)
+    cases = U.golden_cases()
+    assert sorted(golden.files) == sorted(c["name"] for c in cases) and len(cases) == 11
+    for case in cases:
+        out = U.run_golden_case(case, dev)
+        want = golden[case["name"]]
+        assert out.dtype == np.uint8 and out.shape == want.shape, (case["name"], out.shape, want.shape)
+        assert np.array_equal(out, want), f"{case['name']}: {int((out != want).sum())} of {out.size} bytes differ from the parent commit's"
 
 
 def _text(B, L, seed):

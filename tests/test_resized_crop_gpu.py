@@ -7,6 +7,7 @@ import torch
 from open_clip_amd import ops
 from open_clip_amd.input_pipeline import DeviceBatchPipeline, random_resized_crop_boxes
 from tests import resized_crop_util as U
+from tests.resample_util import SIX_BOXES  # also a case of its golden_cases()
 
 pytestmark = pytest.mark.gpu
 
@@ -26,9 +27,6 @@ def _run(src, boxes, size, dev):
     Ho, Wo = (size, size) if isinstance(size, int) else size
     assert out.dtype == torch.uint8 and tuple(out.shape) == (src.shape[0], Ho, Wo, 3)
     return out.cpu().numpy()
-
-
-SIX_BOXES = [(2, 2, 16, 16), (0, 0, 40, 52), (3, 5, 31, 37), (1, 7, 9, 11), (24, 36, 16, 16), (7, 9, 1, 1)]
 
 
 def test_six_boxes_in_one_launch(dev):

@@ -15,7 +15,10 @@ extern "C" {
 
 /* kernel choice of ocn_gemm_nt / ocn_gemm_tn_accum (process-global):
  *   bits 0..3  NT kernel: 0 auto, 4 the general 256x256 ring kernel, 5 the persistent 256x256 kernel (falls back to 4)
- *   bits 4..7  TN kernel: 0 auto, 1 the general 128x128 kernel, 3 the hand-scheduled 256x256 kernel (falls back to 1)
+ *   bits 4..7  TN kernel: 0 auto, 1 the general 128x128 kernel, 3 the hand-scheduled 256x256 kernel (falls back to 1),
+ *              6 / 7 the hand-scheduled kernel with its v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16 main loop (fall back to 1 exactly as 3
+ *              does; single, paired and rescue launches alike).  0 and 3 run the form that ships as default (16x16x32: profiles/tn5_mfma_shape.json);
+ *              both forms are in the product library so that the choice can be re-measured in one process (tools/ab_tn_mfma_shape.py)
  *   bits 8..   developer knobs of the persistent NT kernel: (v >> 8) & 1 skip GELU arithmetic (results wrong), & 2 / & 8 flip the
  *              epilogue's store / load cache policy, & 4 drain stores per tile, & 16 non-temporal A-operand loads, & 32 / & 128 drop the
  *              epilogue's stores / operand loads (results wrong), & 64 timeline build, & 0x200000 whole tail tiles instead of half tiles,
@@ -29,7 +32,8 @@ int ocn_set_gemm_variant(int nt_variant);
 /* developer knobs (process-global; experiments and A/B measurements of tools/sweep.py, never needed by a user):
  *   key 1  attention-backward ablation mask (1 skip the input staging, 2 skip the arithmetic, 4 skip the stores: results wrong)
  *   key 3  persistent NT GEMM (developer build): which workgroups share a start-stagger class: 0 consecutive workgroups alternate (shipped), 1 per XCD, 2 per tile row of the band
- *   key 2  attention backward: 4 = two-pass dK / dV build, 5 = one-pass build (default: two-pass up to 4 waves)   key 4  wgrad GEMM: 1 = skip the atomic epilogue
+ *   key 2  attention backward: 4 = two-pass dK / dV build, 5 = one-pass build (default: two-pass up to 4 waves)   key 4  wgrad GEMM: 1 = skip the atomic epilogue,
+ *          4 = (developer build) stamp s_memtime / s_memrealtime around the main loop; ocn_debug_nt5_trace then returns those stamps (tools/ab_tn_mfma_shape.py --stamps)
  *   key 5  attention backward: extra KiB of LDS per workgroup (occupancy probe)  key 6  1 = generic instead of causal bwd kernel
  *   key 7  1 = always the streamed (explicit head_dim) attention kernels, 2 = always the head-resident ones (head_dim 64, L <= 320)
  *   key 8  1 = LayerNorm backward, default cache policy

@@ -414,7 +414,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTnArgs a) {
     }
 }
 
-int g_tn_variant = 0;  // 0 = auto, 1 = general 128x128 kernel, 3 = 256x256 hand-scheduled (gemm_tn5.hip)
+int g_tn_variant = 0;  // 0 = auto, 1 = general 128x128 kernel, 3 = 256x256 hand-scheduled (gemm_tn5.hip), 6 / 7 = the same with its 32x32x16 / 16x16x32 main loop
+// MFMA shape of the hand-scheduled kernel's main loop under variants 0 and 3: the form with the lower summed wall time over the step's wgrad
+// launches (profiles/tn5_mfma_shape.json); 6 and 7 keep both selectable in one process
+constexpr int TN5_DEFAULT_MF16 = 1;
+inline bool tn_hand_forced() { return g_tn_variant == 3 || g_tn_variant == 6 || g_tn_variant == 7; }
+inline int tn_mf16() { return g_tn_variant == 7 ? 1 : (g_tn_variant == 6 ? 0 : TN5_DEFAULT_MF16); }
 int g_nt_ablate = 0;
 int g_nt_variant = 0;  // 0 = auto, 4 = general 256x256 ring kernel (any M, N; K % 32), 5 = persistent 256x256 (gemm_nt5.hip; K % 128)
 
@@ -560,6 +565,7 @@ int tn_accum(const void* A, int lda, const void* B, int ldb, float* dW, int ldw,
     GemmTnArgs a;
     a.A = (const bf16*)A; a.B = (const bf16*)B; a.dW = dW; a.dbias = dbias;
     a.lda = lda; a.ldb = ldb; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.alpha = alpha; a.ablate = 0; a.nsplit = 0; a.ws = nullptr;
+    a.mf16 = tn_mf16();
     const long need = det ? ocn_tn5_workspace_bytes(M, N, K) : 0;
     if (det && need > 0) {
         OCN_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)dW & 15) == 0 && ldw % 4 == 0,
@@ -567,7 +573,7 @@ int tn_accum(const void* A, int lda, const void* B, int ldb, float* dW, int ldw,
         a.ws = (float*)workspace;
     }
     const bool big = (long)M * N * K >= (1L << 31) && N >= 256 && K >= 256;
-    if ((!det && (g_tn_variant == 3 || (g_tn_variant == 0 && big))) || (det && need > 0)) {  // hand-scheduled 256x256 kernel (gemm_tn5.hip); falls through if the shape does not fit it
+    if ((!det && (tn_hand_forced() || (g_tn_variant == 0 && big))) || (det && need > 0)) {  // hand-scheduled 256x256 kernel (gemm_tn5.hip); falls through if the shape does not fit it
         const int rc = ocn_launch_tn5(a, (hipStream_t)stream);
         if (rc < 0) ocn_set_error("ocn_gemm_tn_accum: launch failed");
         if (rc <= 0) return rc;
@@ -614,11 +620,12 @@ extern "C" int ocn_gemm_tn_accum2(const void* A1, int lda1, const void* B1, int 
     OCN_CHECK_ARG(M > 0 && N1 > 0 && N2 > 0 && K > 0, "ocn_gemm_tn_accum2: bad shape M=%d N1=%d N2=%d K=%d", M, N1, N2, K);
     const bool big = (long)M * (N1 + N2) * K >= (1L << 31) && N1 >= 256 && N2 >= 256 && K >= 256;
     const bool aligned = (((uintptr_t)A1 | (uintptr_t)B1 | (uintptr_t)A2 | (uintptr_t)B2) & 15) == 0;
-    if (big && aligned && (g_tn_variant == 0 || g_tn_variant == 3) && g_ocn_tuning[13] != 1) {  // developer knob 13 = 1: never pair
+    if (big && aligned && (g_tn_variant == 0 || tn_hand_forced()) && g_ocn_tuning[13] != 1) {  // developer knob 13 = 1: never pair
         GemmTnArgs a;
         a.A = (const bf16*)A1; a.B = (const bf16*)B1; a.dW = dW1; a.dbias = dbias1; a.lda = lda1; a.ldb = ldb1; a.ldw = ldw1; a.N = N1;
         a.A2 = (const bf16*)A2; a.B2 = (const bf16*)B2; a.dW2 = dW2; a.dbias2 = dbias2; a.lda2 = lda2; a.ldb2 = ldb2; a.ldw2 = ldw2; a.N2 = N2;
         a.M = M; a.K = K; a.alpha = alpha; a.ablate = 0; a.nsplit = 0; a.ws = nullptr;
+        a.mf16 = tn_mf16();
         const int rc = ocn_launch_tn5_pair(a, (hipStream_t)stream);
         if (rc < 0) ocn_set_error("ocn_gemm_tn_accum2: launch failed");
         if (rc <= 0) return rc;

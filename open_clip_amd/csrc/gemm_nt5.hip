@@ -1057,6 +1057,7 @@ int launch5(GemmNtArgs a, hipStream_t st) {
 
 extern "C" int ocn_debug_nt5_trace(long long* host_out /*[1024]*/) {
 #ifdef OCN_DEV_BUILD
+    if (g_ocn_tuning[4] & 4) return ocn_tn5_debug_stamps(host_out);  // the wgrad kernel's main-loop stamps (gemm_tn5.hip)
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_nt5_trace), sizeof(long long) * 1024) == hipSuccess ? OCN_OK : OCN_ERR_LAUNCH;
 #else
     (void)host_out;

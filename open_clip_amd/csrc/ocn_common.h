@@ -1,5 +1,5 @@
 // Shared device/host helpers for the gfx950 (MI355X, CDNA4) CLIP kernels.
-// wave = 64 lanes everywhere; MFMA = v_mfma_f32_32x32x16_bf16 (fp32 accumulate).
+// wave = 64 lanes everywhere; MFMA = v_mfma_f32_32x32x16_bf16 (fp32 accumulate), and v_mfma_f32_16x16x32_bf16 in the wgrad kernel's main loop.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -75,6 +75,12 @@ OCN_DEV f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mf
 
 // row of accumulator register `reg` (0..15) of a 32x32 MFMA result for this lane; column = lane & 31
 OCN_DEV int mfma32_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
+// v_mfma_f32_16x16x32_bf16: lane l holds A[row l & 15][k = 8 (l >> 4) + j] and B[k = 8 (l >> 4) + j][col l & 15], j = 0..7
+OCN_DEV f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+
+// row of accumulator register `reg` (0..3) of a 16x16 MFMA result for this lane; column = lane & 15
+OCN_DEV int mfma16_row(int reg, int lane) { return (lane >> 4) * 4 + reg; }
 
 // erf-GELU (nn.GELU(), reference transformer.py:295-299) and its derivative, gelu(x) AND gelu'(x) from one evaluation of the shared parts (the
 // forward GELU epilogue saves the derivative for the backward).  The GEMM epilogue that applies it is VALU-issue bound with every MFMA pipe idle

@@ -71,8 +71,9 @@ const char* ocn_last_error(void);
  *   111            NAdamW optimizer: new ocn_nadamw_multi (no signature changed).
  *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed).
  *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed).
- *   114            ragged sources and the validation transform on the device: new ocn_resample_u8 (no signature changed). */
-#define OCN_ABI_VERSION 114
+ *   114            ragged sources and the validation transform on the device: new ocn_resample_u8 (no signature changed).
+ *   115            model EMA: new ocn_ema_lerp_multi (no signature changed). */
+#define OCN_ABI_VERSION 115
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -455,6 +456,18 @@ int ocn_nadamw_multi(const void* entries, const void* chunks, int n_chunks, floa
 /* chunk_ws == NULL: every chunk adds its partial sum to out[0] with an fp32 atomic (order varies from run to run).  chunk_ws = n_chunks floats:
  * the reproducible form -- every chunk stores its partial, one workgroup adds them in chunk order (clip_grad_norm_ under deterministic=True). */
 int ocn_sumsq_multi(const void* entries, const void* chunks, int n_chunks, float* out, float* chunk_ws, ocn_stream_t stream);
+/* Model EMA (open_clip_amd/ema.py::NativeModelEma): ema = lerp(ema, src, weight) over every tensor of a model in one launch.  `entries` = device
+ * array of 32-byte records
+ *   { float* ema; const float* src; int64 numel; int32 mode, pad; }
+ * `chunks` = device array of int32 pairs {entry, index}: 8192-element ranges of the entry, as ocn_adamw_multi's (mode 0 = 16-byte vectors: both
+ * pointers on 16 bytes; mode 2 = scalar, for a pointer off that grid; the numel % 4 tail of a mode-0 tensor is done element by element).  Per
+ * element, in fp32, torch.lerp's two-branch form -- with d = src - ema:
+ *   ema = weight < 0.5 ? ema + weight * d : src - d * (1 - weight)
+ * so both limits are exact: weight == 1 leaves ema == src and weight == 0 leaves ema untouched, bit for bit (for finite values).  weight is
+ * 1 - decay of the average; 1 - weight is formed in fp32.  8 B read + 4 B written per element; no atomics, no LDS, no host synchronisation: the
+ * update is bit-reproducible.  ema and src of one entry must not overlap, nor may two entries' ema ranges.  n_chunks == 0 launches nothing; null
+ * tables, n_chunks < 0 and a non-finite weight are refused before any launch. */
+int ocn_ema_lerp_multi(const void* entries, const void* chunks, int n_chunks, float weight, ocn_stream_t stream);
 
 /* ---- Muon (open_clip_amd/optim.py::NativeMuon) ---------------------------------------------------
  * ocn_gemm_nt_batched: `batch` equal-shape problems in one launch, problem i at base + i * stride (elements):

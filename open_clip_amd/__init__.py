@@ -7,6 +7,7 @@ Public surface (mirrors the reference names):
     create_task, create_loss            <- open_clip.factory.create_task / create_loss (the reference's task classes around the native losses)
     create_optimizer, OptimizerCfg      <- open_clip_train.optim.create_optimizer / OptimizerCfg (the reference's parameter groups around the native
                                            optimizers NativeAdamW, NativeNAdamW, NativeMuon: open_clip_amd.optim)
+    NativeModelEma, setup_ema           <- timm.utils.ModelEmaV3 as open_clip.task.TrainingTask.setup_ema uses it (open_clip_amd.ema: one launch per update)
     get_clip_metrics, zero_shot_accuracy, paired_retrieval_ranks, label_ranks
                                         <- open_clip_train.metrics.get_clip_metrics / open_clip_train.zero_shot.accuracy (open_clip_amd.metrics)
 """
@@ -29,4 +30,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("NativeAdamW", "NativeNAdamW", "NativeMuon", "muon_param_groups", "create_optimizer", "OptimizerCfg"):
         from . import optim
         return getattr(optim, name)
+    if name in ("NativeModelEma", "setup_ema"):
+        from . import ema
+        return getattr(ema, name)
     raise AttributeError(name)

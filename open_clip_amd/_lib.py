@@ -67,6 +67,7 @@ SIGNATURES = {
     "ocn_adamw_multi": [_p, _p, _i, _f, _f, _f, _p, _f, _p],
     "ocn_nadamw_multi": [_p, _p, _i, _f, _f, _f, _f, _p, _f, _p],
     "ocn_sumsq_multi": [_p, _p, _i, _p, _p, _p],
+    "ocn_ema_lerp_multi": [_p, _p, _i, _f, _p],
     "ocn_gemm_nt_batched": [_p, _i, _l, _p, _i, _l, _p, _i, _l, _p, _i, _l, _p, _i, _l, _i, _i, _i, _i, _f, _f, _p],
     "ocn_muon_momentum_multi": [_p, _i, _p, _i, _f, _i, _p, _f, _p, _p, _p],
     "ocn_muon_normalize_multi": [_p, _p, _i, _f, _i, _p, _f, _p, _p],
@@ -98,7 +99,7 @@ DEBUG_SIGNATURES = {
 _SPECIAL = {"ocn_last_error": ([], ctypes.c_char_p), "ocn_version": ([], _i), "ocn_gemm_tn_det_workspace_bytes": ([_i, _i, _i], _l),
             "ocn_fused_logits_ce_workspace_floats": ([_i, _i], _l), "ocn_gemm_nt_splitk_plan": ([_i, _i, _i], _i), "ocn_layernorm_bwd_det_workspace_floats": ([_i, _i], _l), "ocn_get_tile_rescue": ([], _i)}
 
-ABI_VERSION = 114  # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
+ABI_VERSION = 115 # == OCN_ABI_VERSION of include/openclip_hip.h (tests/test_cabi.py compares the two): load() refuses any other library
 
 _lib = None
 _lock = threading.Lock()

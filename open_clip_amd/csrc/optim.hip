@@ -3,6 +3,8 @@
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include <cmath>
+
 namespace {
 
 __global__ void cast_kernel(const float* __restrict__ src, bf16* __restrict__ dst, long n) {
@@ -259,6 +261,47 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict
     if (threadIdx.x == 0) out[0] += ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// ---- model EMA: the weight average of the whole model in ONE launch (open_clip_amd/ema.py::NativeModelEma) -----------------------------------
+// The chunk walk of adam_multi_kernel (8192 consecutive elements per workgroup; mode 0: 16-byte vectors, mode 2: scalar for a pointer off the
+// 16-byte grid) over two pointers per tensor.  Pure streaming: 8 B read + 4 B written per element, no LDS, no atomics.
+struct EmaEntry {
+    float* ema;
+    const float* src;
+    long numel;
+    int mode, pad;
+};
+static_assert(sizeof(EmaEntry) == 32, "EmaEntry layout is mirrored by open_clip_amd/ema.py");
+
+// torch.lerp's two-branch form: both limits are exact (weight 0 leaves e, weight 1 gives s, bit for bit)
+OCN_DEV float ema_one(float e, float s, float weight, float omw) {
+    const float d = s - e;
+    return weight < 0.5f ? e + weight * d : s - d * omw;
+}
+
+__global__ __launch_bounds__(256) void ema_lerp_multi_kernel(const EmaEntry* __restrict__ entries, const int2* __restrict__ chunks, float weight,
+                                                             float omw) {
+    const int2 ch = chunks[blockIdx.x];
+    const EmaEntry e = entries[ch.x];
+    const long base = (long)ch.y * ADAM_CHUNK;
+    const long end = base + ADAM_CHUNK < e.numel ? base + ADAM_CHUNK : e.numel;
+    if (e.mode == 0) {
+        for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) {
+            f32x4 a4 = *(const f32x4*)(e.ema + i);
+            const f32x4 s4 = *(const f32x4*)(e.src + i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a4[j] = ema_one(a4[j], s4[j], weight, omw);
+            *(f32x4*)(e.ema + i) = a4;
+        }
+        const long tail = end - ((end - base) & 3);  // numel % 4 leftovers of the last chunk
+        if (tail + threadIdx.x < end) {
+            const long i = tail + threadIdx.x;
+            e.ema[i] = ema_one(e.ema[i], e.src[i], weight, omw);
+        }
+    } else {
+        for (long i = base + threadIdx.x; i < end; i += 256) e.ema[i] = ema_one(e.ema[i], e.src[i], weight, omw);
+    }
+}
+
 int grid_for(long items, int block) {
     long g = (items + block - 1) / block;
     return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);
@@ -339,5 +382,16 @@ extern "C" int ocn_sumsq_multi(const void* entries, const void* chunks, int n_ch
         hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, chunk_ws, n_chunks, out);
         OCN_CHECK_LAUNCH("ocn_sumsq_multi (fold)");
     }
+    return OCN_OK;
+}
+
+extern "C" int ocn_ema_lerp_multi(const void* entries, const void* chunks, int n_chunks, float weight, ocn_stream_t stream) {
+    OCN_CHECK_ARG(entries && chunks, "ocn_ema_lerp_multi: null entry / chunk table");
+    OCN_CHECK_ARG(n_chunks >= 0, "ocn_ema_lerp_multi: n_chunks must not be negative");
+    OCN_CHECK_ARG(std::isfinite(weight), "ocn_ema_lerp_multi: weight must be finite");
+    if (n_chunks == 0) return OCN_OK;
+    hipLaunchKernelGGL(ema_lerp_multi_kernel, dim3(n_chunks), dim3(256), 0, (hipStream_t)stream, (const EmaEntry*)entries, (const int2*)chunks,
+                       weight, 1.0f - weight);
+    OCN_CHECK_LAUNCH("ocn_ema_lerp_multi");
     return OCN_OK;
 }

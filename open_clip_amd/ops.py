@@ -673,6 +673,11 @@ def adamw_step(w, g, m, v, lr, beta1, beta2, eps, weight_decay, step, w_bf16=Non
               int(step), _chk(clip_coef, F32, "clip_coef"), _stream())
 
 
+def ema_lerp_multi(entries, chunks, n_chunks, weight):
+    """ema = lerp(ema, src, weight) for every record of ``entries`` in one launch (ocn_ema_lerp_multi; tables as ema.py::ema_plan builds them)"""
+    _lib.call("ocn_ema_lerp_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), float(weight), _stream())
+
+
 # ---- Muon (optim.py::NativeMuon) ------------------------------------------------------------------------------------
 def _chk3d(t, name):
     """bf16 [batch, rows, cols], unit inner stride, any row / batch stride -> (ptr, ld, batch stride)"""

@@ -164,9 +164,6 @@ struct MuonEntry {
 };
 static_assert(sizeof(MuonEntry) == 96, "MuonEntry layout is mirrored by open_clip_amd/optim.py");
 
-OCN_DEV float muon_clip(const float* gnorm_sq, float max_norm) {
-    return gnorm_sq ? fminf(1.0f, max_norm / (sqrtf(*gnorm_sq) + 1e-6f)) : 1.0f;  // torch.nn.utils.clip_grad_norm_
-}
 // the update direction from the clipped gradient and the UPDATED buffer (one definition: momentum and normalize must agree to the bit)
 OCN_DEV float muon_u(float g, float buf, float momentum, int nesterov) { return nesterov ? __fmaf_rn(momentum, buf - g, g) : buf; }
 
@@ -185,7 +182,7 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const MuonEntry* __r
     const int2 ch = chunks[blockIdx.x];
     const MuonEntry e = entries[ch.x];
     const TilePos p = tile_pos(e, ch.y);
-    const float gs = muon_clip(gnorm_sq, max_norm);
+    const float gs = grad_clip_coef(gnorm_sq, max_norm);
     float s = 0.f;
     const int c = p.c0 + p.tx;
     if (c < e.cols)
@@ -202,10 +199,8 @@ __global__ __launch_bounds__(256) void muon_momentum_kernel(const MuonEntry* __r
                 s = __fmaf_rn(u, u, s);
             }
         }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_ws[e.chunk0 + ch.y] = ((red[0] + red[1]) + red[2]) + red[3];
+    const float t = block_sum_256(s, red);
+    if (threadIdx.x == 0) chunk_ws[e.chunk0 + ch.y] = t;
 }
 
 // inv_norm[i] = 1 / (sqrt(sum of matrix i's partials) + 1e-7): one workgroup per matrix, the additions in one fixed order (as sumsq_fold_kernel)
@@ -215,10 +210,8 @@ __global__ __launch_bounds__(256) void muon_fold_kernel(const MuonEntry* __restr
     const MuonEntry e = entries[blockIdx.x];
     float s = 0.f;
     for (int i = threadIdx.x; i < e.nchunks; i += 256) s += chunk_ws[e.chunk0 + i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) inv_norm[blockIdx.x] = 1.0f / (sqrtf(((red[0] + red[1]) + red[2]) + red[3]) + 1e-7f);
+    const float t = block_sum_256(s, red);
+    if (threadIdx.x == 0) inv_norm[blockIdx.x] = 1.0f / (sqrtf(t) + 1e-7f);
 }
 
 // X = bf16(u * inv_norm) into both workspace images; everything of the tile inside the padded images and outside the matrix is written as zero
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(256) void muon_normalize_kernel(const MuonEntry* __
     const int2 ch = chunks[blockIdx.x];
     const MuonEntry e = entries[ch.x];
     const TilePos p = tile_pos(e, ch.y);
-    const float gs = muon_clip(gnorm_sq, max_norm), inv = inv_norm[ch.x];
+    const float gs = grad_clip_coef(gnorm_sq, max_norm), inv = inv_norm[ch.x];
     const int rp = (e.rows + 31) & ~31, cp = (e.cols + 31) & ~31;  // padded extents: rp <= ldt, cp <= ldn
     const int c = p.c0 + p.tx;
 #pragma unroll 4

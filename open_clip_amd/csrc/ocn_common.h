@@ -54,6 +54,18 @@ OCN_DEV float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// the sum of s over the 256 threads (four waves) of a workgroup in ONE fixed order -- the wave butterflies, four LDS slots `red`, then
+// ((r0 + r1) + r2) + r3: the same additions in the same order in every run.  Every thread must call it (it holds a barrier); thread 0 uses the result.
+OCN_DEV float block_sum_256(float s, float* red) {
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+// torch.nn.utils.clip_grad_norm_'s coefficient from the squared gradient norm a kernel left on the device (null: no clip)
+OCN_DEV float grad_clip_coef(const float* gnorm_sq, float max_norm) {
+    return gnorm_sq ? fminf(1.0f, max_norm / (sqrtf(*gnorm_sq) + 1e-6f)) : 1.0f;
+}
 OCN_DEV float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

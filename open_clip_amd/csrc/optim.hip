@@ -57,10 +57,8 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x,
         const float v = x[n4 * 4 + threadIdx.x];
         s += v * v;
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(out, red[0] + red[1] + red[2] + red[3]);
+    const float t = block_sum_256(s, red);
+    if (threadIdx.x == 0) unsafeAtomicAdd(out, t);
 }
 
 // torch.optim.AdamW (single-tensor form): p *= 1 - lr*wd; m,v EMA; p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
@@ -88,7 +86,7 @@ __global__ void adamw_kernel(float* __restrict__ w, const float* __restrict__ g,
 // elements (mode 0: 16-byte vector path, mode 2: scalar path for odd sizes / alignments) or one 64x64 tile of a 2-D GEMM
 // weight (mode 1).  Besides torch.optim.AdamW's update the kernel refreshes the bf16 operand copies of the GEMM weights in
 // the same pass -- the plain copy [rows, cols] and, in tile mode, the transposed copy [cols, rows] through LDS -- and applies
-// the clip_grad_norm_ coefficient computed from the squared gradient norm that ocn_sumsq_multi left on the device.
+// the clip_grad_norm_ coefficient (grad_clip_coef, ocn_common.h) of the squared gradient norm that ocn_sumsq_multi left on the device.
 struct AdamEntry {
     float* w;
     const float* g;
@@ -104,7 +102,7 @@ struct AdamEntry {
     union { float bc1; float c_g; };       // 1 - beta1^step          | lr (1 - mu_t) / (1 - mu_product)
     union { float bc2_sqrt; float c_m; };  // sqrt(1 - beta2^step)    | lr mu_next / (1 - mu_product mu_next)
 };
-static_assert(sizeof(AdamEntry) == 88, "AdamEntry layout is mirrored by open_clip_amd/optim.py");
+static_assert(sizeof(AdamEntry) == 88, "AdamEntry layout is mirrored by open_clip_amd/tables.py");
 constexpr int ADAM_CHUNK = 8192;
 
 // omb1 / omb2: 1 - beta1 / 1 - beta2 as the entry point hands them over (ocn_adamw_multi: the fp32 differences; ocn_nadamw_multi: the caller's)
@@ -135,7 +133,34 @@ OCN_DEV float update_one(const AdamEntry& e, float w, float gi, float& m, float&
     else return adam_one(w, gi, m, v, e.lr, e.wd, omb1, b2, omb2, eps, e.bc1, e.bc2_sqrt);
 }
 
-// one walk over the chunk table for every update rule: RULE picks the element update, everything else (modes, operand copies, clip) is shared
+// the walk of one {numel, index, mode} chunk outside tile mode: ADAM_CHUNK consecutive elements per workgroup of 256 threads.  Mode 0: quad(i) on
+// 16-byte vectors, i = base + 4 t, + 1024, ..., then one(i) on the numel % 4 leftovers of the last chunk; any other mode: one(i), i = base + t, + 256, ...
+template <typename Quad, typename One>
+OCN_DEV void chunk_walk(long numel, int index, int mode, Quad quad, One one) {
+    const long base = (long)index * ADAM_CHUNK;
+    const long end = base + ADAM_CHUNK < numel ? base + ADAM_CHUNK : numel;
+    if (mode == 0) {
+        for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) quad(i);
+        const long tail = end - ((end - base) & 3);
+        if (tail + threadIdx.x < end) one(tail + threadIdx.x);
+    } else {
+        for (long i = base + threadIdx.x; i < end; i += 256) one(i);
+    }
+}
+
+// one element: load, update, store w, m, v and the plain bf16 copy -- the numel % 4 leftovers of the vector path and the whole scalar path
+template <int RULE>
+OCN_DEV void adam_single(const AdamEntry& e, long i, float gs, float omb1, float b2, float omb2, float eps) {
+    float mi = e.m[i], vi = e.v[i];
+    const float p = update_one<RULE>(e, e.w[i], e.g[i] * gs, mi, vi, omb1, b2, omb2, eps);
+    e.w[i] = p; e.m[i] = mi; e.v[i] = vi;
+    if (e.w16n) e.w16n[i] = f2bf(p);
+}
+
+// one walk over the chunk table for every update rule: RULE picks the element update, everything else (modes, operand copies, clip) is shared.
+// The two four-element loops (tile mode, vector path) and the walk of modes 0 / 2 stay written out in the kernel body: behind adam_quad / chunk_walk
+// (as a function or as a lambda) the compiler pairs the lanes of  v * b2 + g * g * omb2  the other way round in the vector path and contracts the
+// other product into the FMA -- exp_avg_sq moves by an ulp in a quarter of the elements (tests/test_optim_parent_gpu.py).
 template <int RULE>
 __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __restrict__ entries, const int2* __restrict__ chunks,
                                                          float omb1, float b2, float omb2, float eps, const float* __restrict__ gnorm_sq,
@@ -143,8 +168,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __rest
     __shared__ float tile[64][65];
     const int2 ch = chunks[blockIdx.x];
     const AdamEntry e = entries[ch.x];
-    float gs = 1.0f;
-    if (gnorm_sq) gs = fminf(1.0f, max_norm / (sqrtf(*gnorm_sq) + 1e-6f));  // torch.nn.utils.clip_grad_norm_
+    const float gs = grad_clip_coef(gnorm_sq, max_norm);
     if (e.mode == 1) {
         const int tiles_c = e.cols >> 6;
         const int r0 = (ch.y / tiles_c) * 64, c0 = (ch.y % tiles_c) * 64;
@@ -201,20 +225,9 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const AdamEntry* __rest
             if (e.w16n) *(bf16x4*)(e.w16n + i) = (bf16x4){f2bf(p4[0]), f2bf(p4[1]), f2bf(p4[2]), f2bf(p4[3])};
         }
         const long tail = end - ((end - base) & 3);  // numel % 4 leftovers of the last chunk
-        if (tail + threadIdx.x < end) {
-            const long i = tail + threadIdx.x;
-            float mi = e.m[i], vi = e.v[i];
-            const float p = update_one<RULE>(e, e.w[i], e.g[i] * gs, mi, vi, omb1, b2, omb2, eps);
-            e.w[i] = p; e.m[i] = mi; e.v[i] = vi;
-            if (e.w16n) e.w16n[i] = f2bf(p);
-        }
+        if (tail + threadIdx.x < end) adam_single<RULE>(e, tail + threadIdx.x, gs, omb1, b2, omb2, eps);
     } else {
-        for (long i = base + threadIdx.x; i < end; i += 256) {
-            float mi = e.m[i], vi = e.v[i];
-            const float p = update_one<RULE>(e, e.w[i], e.g[i] * gs, mi, vi, omb1, b2, omb2, eps);
-            e.w[i] = p; e.m[i] = mi; e.v[i] = vi;
-            if (e.w16n) e.w16n[i] = f2bf(p);
-        }
+        for (long i = base + threadIdx.x; i < end; i += 256) adam_single<RULE>(e, i, gs, omb1, b2, omb2, eps);
     }
 }
 
@@ -238,13 +251,10 @@ __global__ __launch_bounds__(256) void sumsq_multi_kernel(const AdamEntry* __res
     } else {
         const long base = (long)ch.y * ADAM_CHUNK;
         const long end = base + ADAM_CHUNK < e.numel ? base + ADAM_CHUNK : e.numel;
-        for (long i = base + threadIdx.x; i < end; i += 256) s += e.g[i] * e.g[i];
+        for (long i = base + threadIdx.x; i < end; i += 256) s += e.g[i] * e.g[i];  // this order is what the fixed-order norm's bits are made of
     }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const float t = block_sum_256(s, red);
     if (threadIdx.x == 0) {
-        const float t = red[0] + red[1] + red[2] + red[3];
         if (chunk_ws) chunk_ws[blockIdx.x] = t; else unsafeAtomicAdd(out, t);
     }
 }
@@ -255,15 +265,13 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(const float* __restrict
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) s += ws[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] += ((red[0] + red[1]) + red[2]) + red[3];
+    const float t = block_sum_256(s, red);
+    if (threadIdx.x == 0) out[0] += t;
 }
 
 // ---- model EMA: the weight average of the whole model in ONE launch (open_clip_amd/ema.py::NativeModelEma) -----------------------------------
-// The chunk walk of adam_multi_kernel (8192 consecutive elements per workgroup; mode 0: 16-byte vectors, mode 2: scalar for a pointer off the
-// 16-byte grid) over two pointers per tensor.  Pure streaming: 8 B read + 4 B written per element, no LDS, no atomics.
+// chunk_walk (8192 consecutive elements per workgroup; mode 0: 16-byte vectors, mode 2: scalar for a pointer off the 16-byte grid) over two
+// pointers per tensor.  Pure streaming: 8 B read + 4 B written per element, no LDS, no atomics.
 struct EmaEntry {
     float* ema;
     const float* src;
@@ -282,27 +290,19 @@ __global__ __launch_bounds__(256) void ema_lerp_multi_kernel(const EmaEntry* __r
                                                              float omw) {
     const int2 ch = chunks[blockIdx.x];
     const EmaEntry e = entries[ch.x];
-    const long base = (long)ch.y * ADAM_CHUNK;
-    const long end = base + ADAM_CHUNK < e.numel ? base + ADAM_CHUNK : e.numel;
-    if (e.mode == 0) {
-        for (long i = base + threadIdx.x * 4; i + 3 < end; i += 1024) {
-            f32x4 a4 = *(const f32x4*)(e.ema + i);
-            const f32x4 s4 = *(const f32x4*)(e.src + i);
+    chunk_walk(e.numel, ch.y, e.mode,
+               [&](long i) {
+                   f32x4 a4 = *(const f32x4*)(e.ema + i);
+                   const f32x4 s4 = *(const f32x4*)(e.src + i);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) a4[j] = ema_one(a4[j], s4[j], weight, omw);
-            *(f32x4*)(e.ema + i) = a4;
-        }
-        const long tail = end - ((end - base) & 3);  // numel % 4 leftovers of the last chunk
-        if (tail + threadIdx.x < end) {
-            const long i = tail + threadIdx.x;
-            e.ema[i] = ema_one(e.ema[i], e.src[i], weight, omw);
-        }
-    } else {
-        for (long i = base + threadIdx.x; i < end; i += 256) e.ema[i] = ema_one(e.ema[i], e.src[i], weight, omw);
-    }
+                   for (int j = 0; j < 4; ++j) a4[j] = ema_one(a4[j], s4[j], weight, omw);
+                   *(f32x4*)(e.ema + i) = a4;
+               },
+               [&](long i) { e.ema[i] = ema_one(e.ema[i], e.src[i], weight, omw); });
 }
 
-int grid_for(long items, int block) {
+// workgroups of a grid-stride launch in this file: at most 4096 (ocn_grid_for's cap is 8192)
+int grid_for_4096(long items, int block) {
     long g = (items + block - 1) / block;
     return (int)(g < 4096 ? (g > 0 ? g : 1) : 4096);
 }
@@ -312,7 +312,7 @@ int grid_for(long items, int block) {
 extern "C" int ocn_cast_f32_bf16(const float* src, void* dst, int64_t n, ocn_stream_t stream) {
     OCN_CHECK_ARG(src && dst && n > 0, "ocn_cast_f32_bf16: bad arguments");
     OCN_CHECK_ARG(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 7) == 0, "ocn_cast_f32_bf16: misaligned");
-    hipLaunchKernelGGL(cast_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, (long)n);
+    hipLaunchKernelGGL(cast_kernel, dim3(grid_for_4096((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, (long)n);
     OCN_CHECK_LAUNCH("ocn_cast_f32_bf16");
     return OCN_OK;
 }
@@ -320,7 +320,7 @@ extern "C" int ocn_cast_f32_bf16(const float* src, void* dst, int64_t n, ocn_str
 extern "C" int ocn_cast_f32_bf16_scaled(const float* src, void* dst, int64_t n, const float* scale_dev, ocn_stream_t stream) {
     OCN_CHECK_ARG(src && dst && n > 0 && scale_dev, "ocn_cast_f32_bf16_scaled: bad arguments");
     OCN_CHECK_ARG(((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 7) == 0, "ocn_cast_f32_bf16_scaled: misaligned");
-    hipLaunchKernelGGL(cast_scaled_kernel, dim3(grid_for((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, (long)n, scale_dev);
+    hipLaunchKernelGGL(cast_scaled_kernel, dim3(grid_for_4096((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, src, (bf16*)dst, (long)n, scale_dev);
     OCN_CHECK_LAUNCH("ocn_cast_f32_bf16_scaled");
     return OCN_OK;
 }
@@ -335,7 +335,7 @@ extern "C" int ocn_cast_transpose_f32_bf16(const float* src, void* dst, int R, i
 extern "C" int ocn_sumsq_accum(const float* x, int64_t n, float* out, ocn_stream_t stream) {
     OCN_CHECK_ARG(x && out && n > 0, "ocn_sumsq_accum: bad arguments");
     OCN_CHECK_ARG(((uintptr_t)x & 15) == 0, "ocn_sumsq_accum: misaligned");
-    int g = grid_for((n + 3) / 4, 256);
+    int g = grid_for_4096((n + 3) / 4, 256);
     if (g > 1024) g = 1024;
     hipLaunchKernelGGL(sumsq_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, (long)n, out);
     OCN_CHECK_LAUNCH("ocn_sumsq_accum");
@@ -348,7 +348,7 @@ extern "C" int ocn_adamw_step(float* w, const float* g, float* m, float* v, void
     OCN_CHECK_ARG(w && g && m && v && n > 0 && step >= 1, "ocn_adamw_step: bad arguments");
     const float bc1 = 1.0f - powf(beta1, (float)step);
     const float bc2_sqrt = sqrtf(1.0f - powf(beta2, (float)step));
-    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (bf16*)w_bf16, (long)n,
+    hipLaunchKernelGGL(adamw_kernel, dim3(grid_for_4096(n, 256)), dim3(256), 0, (hipStream_t)stream, w, g, m, v, (bf16*)w_bf16, (long)n,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, clip_coef);
     OCN_CHECK_LAUNCH("ocn_adamw_step");
     return OCN_OK;

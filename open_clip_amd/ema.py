@@ -3,7 +3,7 @@
 ``state_dict_for_inference``, :439-443; every ``eval_forward``, clip_task.py:48-50; task/checkpoint.py:81-82, 118-119), without timm.
 
 ``NativeModelEma`` holds a deep copy of the model in eval mode (``.module``) and averages into it with ONE launch per update over the whole model
-(``ocn_ema_lerp_multi``, include/openclip_hip.h: torch.lerp's two-branch form, fp32): the pointer table of the optimizers (``optim._Table``), 8192-element
+(``ocn_ema_lerp_multi``, include/openclip_hip.h: torch.lerp's two-branch form, fp32): the pointer table of the optimizers (``tables.PinnedTable``), 8192-element
 chunks, built once and revalidated against both sides' addresses on every update.  The constructor's options carry the names timm's ModelEmaV3 uses as
 far as is known here; timm is not a dependency and nothing was compared with it, so this module -- not timm -- defines what they mean:
 
@@ -22,8 +22,8 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
-from .optim import _CHUNK, _Table, unwrap_model
+from . import ops, tables
+from .optim import unwrap_model
 
 # EmaEntry of csrc/optim.hip
 _EMA_ENTRY = np.dtype([("ema", "<u8"), ("src", "<u8"), ("numel", "<i8"), ("mode", "<i4"), ("pad", "<i4")])
@@ -34,16 +34,10 @@ def ema_plan(triples):
     """the tables of ``ocn_ema_lerp_multi`` from ``(ema_ptr, src_ptr, numel)`` triples, on the host: the records (mode 0 = 16-byte vector path when
     both addresses sit on 16 bytes, else 2 = scalar path) and the chunk list, int32 ``[n_chunks, 2]`` of {entry, index}: ceil(numel / 8192) per entry"""
     ent = np.zeros(len(triples), dtype=_EMA_ENTRY)
-    chunks = [np.empty((0, 2), dtype=np.int32)]
-    for i, (ema_ptr, src_ptr, numel) in enumerate(triples):
-        e = ent[i]
+    for e, (ema_ptr, src_ptr, numel) in zip(ent, triples):
         e["ema"], e["src"], e["numel"] = ema_ptr, src_ptr, numel
         e["mode"] = 0 if ema_ptr % 16 == 0 and src_ptr % 16 == 0 else 2
-        k = -(-numel // _CHUNK)
-        c = np.empty((k, 2), dtype=np.int32)
-        c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
-        chunks.append(c)
-    return ent, np.concatenate(chunks, axis=0)
+    return ent, tables.chunk_list(-(-ent["numel"] // tables.CHUNK))
 
 
 def _device_of(model):
@@ -134,12 +128,12 @@ class NativeModelEma(nn.Module):
             key = tuple((e.data_ptr(), s.data_ptr(), e.numel()) for _, e, s in averaged)
             if key != self._plan_key:
                 ent, chunks = ema_plan(key)
-                self._plan = {"table": _Table(ent, dev), "chunks_dev": torch.from_numpy(chunks).to(dev), "n_chunks": int(chunks.shape[0])}
+                self._plan = {"table": tables.PinnedTable(ent, dev), "chunks_dev": torch.from_numpy(chunks).to(dev), "n_chunks": int(chunks.shape[0])}
                 self._plan_key = key
             plan = self._plan
             # uploaded on every call, like the optimizers' tables: the copy is ordered on the stream the launch goes to, whichever that is this time
             ops.ema_lerp_multi(plan["table"].upload(), plan["chunks_dev"], plan["n_chunks"], weight)
-            torch.autograd.graph.increment_version([e for _, e, _ in averaged])  # raw-pointer update
+            tables.finish([e for _, e, _ in averaged])
         # the twin's cached bf16 operand copies are keyed by (address, version): drop them, as after any write through raw pointers
         invalidate = getattr(self.module, "invalidate_weight_caches", None)
         if callable(invalidate):

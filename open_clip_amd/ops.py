@@ -673,6 +673,24 @@ def adamw_step(w, g, m, v, lr, beta1, beta2, eps, weight_decay, step, w_bf16=Non
               int(step), _chk(clip_coef, F32, "clip_coef"), _stream())
 
 
+def sumsq_multi(entries, chunks, n_chunks, out, chunk_ws=None):
+    """out[0] += sum of g^2 over an AdamEntry table (ocn_sumsq_multi; tables.py::AdamTables); ``chunk_ws`` fp32 [n_chunks]: the fixed-order form"""
+    _lib.call("ocn_sumsq_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), _chk(out, F32, "out"),
+              _chk(chunk_ws, F32, "chunk_ws"), _stream())
+
+
+def adamw_multi(entries, chunks, n_chunks, beta1, beta2, eps, gnorm_sq=None, max_norm=0.0):
+    """torch.optim.AdamW's update of every chunk in one launch, operand copies included (ocn_adamw_multi); ``gnorm_sq``: the clip's squared norm"""
+    _lib.call("ocn_adamw_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), float(beta1), float(beta2),
+              float(eps), _chk(gnorm_sq, F32, "gnorm_sq"), float(max_norm), _stream())
+
+
+def nadamw_multi(entries, chunks, n_chunks, one_minus_beta1, beta2, one_minus_beta2, eps, gnorm_sq=None, max_norm=0.0):
+    """torch.optim.NAdam(decoupled_weight_decay=True)'s update over the same tables (ocn_nadamw_multi)"""
+    _lib.call("ocn_nadamw_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), float(one_minus_beta1),
+              float(beta2), float(one_minus_beta2), float(eps), _chk(gnorm_sq, F32, "gnorm_sq"), float(max_norm), _stream())
+
+
 def ema_lerp_multi(entries, chunks, n_chunks, weight):
     """ema = lerp(ema, src, weight) for every record of ``entries`` in one launch (ocn_ema_lerp_multi; tables as ema.py::ema_plan builds them)"""
     _lib.call("ocn_ema_lerp_multi", _chk(entries, torch.uint8, "entries"), _chk(chunks, torch.int32, "chunks"), int(n_chunks), float(weight), _stream())

@@ -27,15 +27,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops, tables
 
-_ENTRY = np.dtype([("w", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("w16n", "<u8"), ("w16t", "<u8"), ("numel", "<i8"),
-                   ("rows", "<i4"), ("cols", "<i4"), ("mode", "<i4"), ("pad", "<i4"),
-                   ("lr", "<f4"), ("wd", "<f4"), ("bc1", "<f4"), ("bc2_sqrt", "<f4")])
-# the same record as ocn_nadamw_multi reads it: the four floats under NAdamW's names (the unions of AdamEntry, csrc/optim.hip)
-_NADAM_ENTRY = np.dtype(_ENTRY.descr[:-4] + [("decay", "<f4"), ("bc2", "<f4"), ("c_g", "<f4"), ("c_m", "<f4")])
-assert _ENTRY.itemsize == _NADAM_ENTRY.itemsize == 88
-_CHUNK = 8192
 DEFAULT_FALLBACK = ("token_embedding.weight", "positional_embedding", "visual.positional_embedding", "visual.class_embedding", "logit_scale", "logit_bias")
 
 
@@ -140,34 +133,12 @@ def weight_caches_of(model):
 
 
 # ---- AdamW / NAdamW: one launch over the whole model --------------------------------------------------------------------------------------
-class _Table:
-    """a record table that travels host -> device every step through one of TWO pinned buffers used alternately: the buffer a step fills was last
-    read by the upload of two steps ago, so the wait never blocks a host that runs a step ahead of the device"""
-
-    def __init__(self, records, dev):
-        self.records = records
-        nbytes = records.size * records.dtype.itemsize
-        self.host = [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        self.copied, self.turn = [None, None], 0
-
-    def upload(self):
-        turn, self.turn = self.turn, 1 - self.turn
-        if self.copied[turn] is not None and not self.copied[turn].query():
-            self.copied[turn].synchronize()  # the upload of two steps ago out of this pinned buffer (in practice long finished)
-        self.host[turn].numpy()[:] = self.records.view(np.uint8).reshape(-1)
-        self.dev.copy_(self.host[turn], non_blocking=True)
-        self.copied[turn] = torch.cuda.Event()
-        self.copied[turn].record()
-        return self.dev
-
-
 class _TableAdam(torch.optim.Optimizer):
-    """what NativeAdamW and NativeNAdamW share: the per-parameter state, the plan (records, modes, chunk list, operand copies), the pinned upload, the
-    fused clip and the launch.  A subclass names its entry point (``_KERNEL``), its record dtype (``_RECORD``), its scalar state (``_SCALARS``: key ->
-    (zero, type)), the group values every group must agree on because they are kernel arguments (``_shared_of``: (beta1, beta2, eps, ...)), and fills
-    the four per-step floats of a record (``_fill``)."""
-    _KERNEL = _WHO = _RECORD = None
+    """what NativeAdamW and NativeNAdamW share: the per-parameter state, the plan (``tables.AdamTables``: records, modes, chunk list, operand copies,
+    pinned upload), the fused clip and the launch.  A subclass names its entry point (``_LAUNCH``), its scalar state (``_SCALARS``: key -> (zero, type)),
+    the group values every group must agree on because they are kernel arguments (``_shared_of``: (beta1, beta2, eps, ...)), and gives the four
+    per-step floats of a record (``_fill``)."""
+    _LAUNCH = _WHO = None
     _SCALARS = {"step": (0, int)}
     _SHARED_TEXT = "betas and eps"
 
@@ -185,116 +156,36 @@ class _TableAdam(torch.optim.Optimizer):
         b1, b2 = group["betas"]
         return float(b1), float(b2), float(group["eps"])
 
-    def _fill(self, e, group, st, shared):
-        raise NotImplementedError
-
     def _kernel_scalars(self, shared):
         """the entry point's float arguments between ``n_chunks`` and ``gnorm_sq``"""
         return shared[:3]
 
-    def _state_of(self, p):
-        st = self.state[p]
-        if not st:
-            for k, (zero, _) in self._SCALARS.items():
-                st[k] = zero
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st
-
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._plan = self._plan_key = None  # the moments are new tensors: rebuild the device table on the next step
-        for st in self.state.values():      # torch stores its scalar state (`step`, NAdam's `mu_product`) as 0-d tensors in its own checkpoints: accept both
-            for k, (_, kind) in self._SCALARS.items():
-                if torch.is_tensor(st.get(k)):
-                    st[k] = kind(st[k].item())
-
-    def _copies_of(self, p):
-        n = t = None
-        for c in self.weight_caches:
-            n = c.peek(p, "n") if n is None else n
-            t = c.peek(p, "t") if t is None else t
-        return n, t
-
-    def _build_plan(self, active):
-        """static part of the step: state tensors, operand copies, modes, chunk list (rebuilt when the set of tensors with
-        a gradient, or the set of cached operand copies, changes)"""
-        dev = active[0][1].device
-        ent = np.zeros(len(active), dtype=self._RECORD)
-        chunks, copies = [], []
-        for i, (group, p) in enumerate(active):
-            st = self._state_of(p)
-            n16, t16 = (None, None) if p.ndim != 2 and not (p.ndim == 4) else self._copies_of(p)
-            rows = p.shape[0] if p.ndim >= 2 else 1
-            cols = p.numel() // rows
-            e = ent[i]
-            e["w"], e["m"], e["v"] = p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-            e["w16n"] = 0 if n16 is None else n16.data_ptr()
-            e["w16t"] = 0 if t16 is None else t16.data_ptr()
-            e["numel"], e["rows"], e["cols"] = p.numel(), rows, cols
-            tile = t16 is not None and rows % 64 == 0 and cols % 64 == 0
-            if t16 is not None and not tile:  # odd-shaped weight: keep its transposed copy on the cast path
-                e["w16t"] = 0
-                t16 = None
-            e["mode"] = 1 if tile else (0 if p.data_ptr() % 16 == 0 else 2)
-            k = (rows // 64) * (cols // 64) if tile else -(-p.numel() // _CHUNK)
-            c = np.empty((k, 2), dtype=np.int32)
-            c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
-            chunks.append(c)
-            copies.append((n16, t16))
-        chunks = np.concatenate(chunks, axis=0)
-        return {"table": _Table(ent, dev), "n_chunks": int(chunks.shape[0]), "copies": copies, "chunks_dev": torch.from_numpy(chunks).to(dev)}
+        tables.scalars_to_host(self.state, {k: kind for k, (_, kind) in self._SCALARS.items()})
 
     @torch.no_grad()
     def _step_tables(self):
         active = [(g, p) for g in self.param_groups for p in g["params"] if p.grad is not None]
         if not active:
             return
-        key = tuple((id(p), tuple(p.shape)) + (tuple(map(id, self._copies_of(p))) if p.ndim in (2, 4) else ()) for _, p in active)
-        if key != self._plan_key:
-            self._plan, self._plan_key = self._build_plan(active), key
-        plan = self._plan
-        ent = plan["table"].records
-        shared = self._shared_of(active[0][0])
-        grads, checked = [], None
-        for i, (group, p) in enumerate(active):
-            if group is not checked:
-                if self._shared_of(group) != shared:
-                    raise RuntimeError(f"{self._WHO}: all param groups must share {self._SHARED_TEXT}")
-                checked = group
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-            grads.append(g)
-            st = self._state_of(p)
-            st["step"] += 1
-            e = ent[i]
-            # every pointer of the record is re-read every step: load_state_dict(), model.to(), `p.data = ...` replace the
-            # parameter / moment tensors behind an unchanged id(p), and a cached address would then update freed memory
-            m, v = st["exp_avg"], st["exp_avg_sq"]
-            if not (m.is_contiguous() and v.is_contiguous() and p.is_contiguous()):
-                raise RuntimeError(f"{self._WHO}: parameters and their moments must be contiguous")
-            if m.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32:
-                st["exp_avg"], st["exp_avg_sq"] = m, v = m.to(p.device, torch.float32), v.to(p.device, torch.float32)
-            e["w"], e["m"], e["v"], e["g"] = p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr()
-            if e["mode"] != 1:
-                e["mode"] = 0 if (p.data_ptr() % 16 == 0 and g.data_ptr() % 16 == 0 and m.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0) else 2
-            self._fill(e, group, st, shared)
-        entries_dev = plan["table"].upload()
-        stream = torch.cuda.current_stream().cuda_stream
-        gn, max_norm = 0, 0.0
-        if self.grad_clip_norm is not None:
-            acc = torch.zeros(1, dtype=torch.float32, device=entries_dev.device)
-            ws = torch.empty(plan["n_chunks"], dtype=torch.float32, device=acc.device) if self.deterministic else None
-            _lib.call("ocn_sumsq_multi", entries_dev.data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], acc.data_ptr(),
-                      0 if ws is None else ws.data_ptr(), stream)
-            self.last_grad_norm_sq = acc
-            gn, max_norm = acc.data_ptr(), float(self.grad_clip_norm)
-        _lib.call(self._KERNEL, entries_dev.data_ptr(), plan["chunks_dev"].data_ptr(), plan["n_chunks"], *self._kernel_scalars(shared), gn, max_norm,
-                  stream)
         params = [p for _, p in active]
-        torch.autograd.graph.increment_version(params)  # raw-pointer update
-        for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launch
-            for c in self.weight_caches:
-                c.mark_fresh(p, n16, t16)
+        copies = [tables.copies_of(self.weight_caches, p) for p in params]
+        # the static part of the step (rebuilt when the set of tensors with a gradient, or the set of cached operand copies, changes)
+        key = tuple((id(p), tuple(p.shape)) + (tuple(map(id, c)) if p.ndim in (2, 4) else ()) for p, c in zip(params, copies))
+        if key != self._plan_key:
+            self._plan, self._plan_key = tables.AdamTables(f"{self._WHO}: parameters and their moments must be contiguous", params, copies), key
+            self._plan.to(params[0].device)
+        plan = self._plan
+        shared = self._shared_of(active[0][0])
+        if any(self._shared_of(group) != shared for group in {id(g): g for g, _ in active}.values()):
+            raise RuntimeError(f"{self._WHO}: all param groups must share {self._SHARED_TEXT}")
+        grads = plan.refresh(active, self.state, self._SCALARS, self._fill, shared)  # held until the launches are queued
+        acc = plan.run(self._LAUNCH, self._kernel_scalars(shared), self.grad_clip_norm, self.deterministic)
+        if acc is not None:
+            self.last_grad_norm_sq = acc
+        tables.finish(params, plan.copies, self.weight_caches)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -304,7 +195,7 @@ class _TableAdam(torch.optim.Optimizer):
 
 
 class NativeAdamW(_TableAdam):
-    _KERNEL, _WHO, _RECORD = "ocn_adamw_multi", "NativeAdamW (fused)", _ENTRY
+    _LAUNCH, _WHO, _fill = staticmethod(ops.adamw_multi), "NativeAdamW (fused)", staticmethod(tables.adamw_fill)
 
     def __init__(self, params, lr=5e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2, grad_clip_norm=None, weight_caches=(),
                  fused=True, deterministic=False):
@@ -331,18 +222,12 @@ class NativeAdamW(_TableAdam):
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                st = self._state_of(p)
+                st = tables.adam_state(self.state, p, self._SCALARS)
                 st["step"] += 1
                 g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 ops.adamw_step(p.view(-1), g.view(-1), st["exp_avg"].view(-1), st["exp_avg_sq"].view(-1), group["lr"], b1, b2,
                                group["eps"], group["weight_decay"], st["step"], clip_coef=coef)
                 torch.autograd.graph.increment_version(p)  # raw-pointer update: let the bf16 weight cache see it
-
-    # ---- fused path ---------------------------------------------------------------------------------------------------
-    def _fill(self, e, group, st, shared):
-        e["lr"], e["wd"] = group["lr"], group["weight_decay"]
-        e["bc1"] = 1.0 - shared[0] ** st["step"]
-        e["bc2_sqrt"] = (1.0 - shared[1] ** st["step"]) ** 0.5
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -370,7 +255,7 @@ class NativeNAdamW(_TableAdam):
     ``mu_product``, ``exp_avg``, ``exp_avg_sq``; the two scalars are host numbers, a torch checkpoint's 0-d tensors are accepted).  ``lr`` is re-read
     every step, a group's extra keys (``lr_scale``, ``group_name``, ...) are carried untouched; ``betas``, ``eps`` and ``momentum_decay`` are kernel
     arguments and must agree across groups.  Only the decoupled form exists: the L2-coupled one is refused."""
-    _KERNEL, _WHO, _RECORD = "ocn_nadamw_multi", "NativeNAdamW", _NADAM_ENTRY
+    _LAUNCH, _WHO = staticmethod(ops.nadamw_multi), "NativeNAdamW"
     _SCALARS = {"step": (0, int), "mu_product": (1.0, float)}
     _SHARED_TEXT = "betas, eps and momentum_decay"
 
@@ -395,13 +280,14 @@ class NativeNAdamW(_TableAdam):
         b1, b2, eps = shared[:3]
         return 1.0 - b1, b2, 1.0 - b2, eps  # 1 - beta formed in double, as torch forms it (include/openclip_hip.h says what the fp32 difference costs)
 
-    def _fill(self, e, group, st, shared):
+    def _fill(self, group, st, shared):
+        """decay, bc2, c_g, c_m: the record's four floats as ocn_nadamw_multi reads them"""
         lr = group["lr"]
         key = (st["step"], st["mu_product"], lr)
         if key != self._schedule[0]:  # the parameters of a group (usually of the whole model) are at the same point of the schedule: evaluate it once
             self._schedule = (key, nadam_schedule(*key, shared[0], shared[1], shared[3]))
-        st["mu_product"], e["c_g"], e["c_m"], e["bc2"] = self._schedule[1]
-        e["decay"] = 1.0 - lr * group["weight_decay"]
+        st["mu_product"], c_g, c_m, bc2 = self._schedule[1]
+        return 1.0 - lr * group["weight_decay"], bc2, c_g, c_m
 
 
 # ---- Muon -------------------------------------------------------------------------------------------------------------------------------
@@ -464,55 +350,26 @@ class NativeMuon(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._plan = self._plan_key = None
-        for st in self.state.values():
-            if torch.is_tensor(st.get("step")):
-                st["step"] = int(st["step"].item())
+        tables.scalars_to_host(self.state, {"step": int})
 
-    def _copies_of(self, p):
-        n = t = None
-        if p.ndim in (2, 4):
-            for c in self.weight_caches:
-                n = c.peek(p, "n") if n is None else n
-                t = c.peek(p, "t") if t is None else t
-        return n, t
+    @staticmethod
+    def _adam_tables(active, copies):
+        """AdamEntry records of EVERY active parameter, flat (never in tile mode): the squared gradient norm runs over all of them, AdamW over the
+        fallback ones, whose transposed copies stay on the cast path; a Muon matrix's copies are rewritten by ocn_muon_apply_multi instead"""
+        is_muon = [takes_muon(g, p) for g, p in active]
+        return tables.AdamTables("NativeMuon: the AdamW moments must be contiguous", [p for _, p in active],
+                                 [(None, None) if m else c for m, c in zip(is_muon, copies)], tiles=False, update=[not m for m in is_muon])
 
-    def _state_of(self, p, muon):
-        st = self.state[p]
-        if not st:
-            if muon:
-                st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-            else:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        return st
+    @staticmethod
+    def _fallback_fill(group, st, shared):
+        return tables.adamw_fill({"lr": group["lr"] * group["fallback_lr_scale"], "weight_decay": group["weight_decay"]}, st, shared)
 
-    def _build_plan(self, active, ns_steps):
-        """static part of the step: state tensors, the Newton-Schulz workspace per padded shape, chunk lists, which operand copies are rewritten"""
+    def _build_plan(self, active, copies, ns_steps):
+        """static part of the step: the AdamW-side tables, the Newton-Schulz workspace per padded shape, chunk lists, which operand copies are rewritten"""
         dev = active[0][1].device
-        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         muon = [i for i, (g, p) in enumerate(active) if takes_muon(g, p)]
-        fb = [i for i, (g, p) in enumerate(active) if not takes_muon(g, p)]
-        plan = {"muon": muon, "fb": fb, "copies": [(None, None)] * len(active)}
-        # AdamEntry records of EVERY active parameter: the squared gradient norm runs over all of them, AdamW over the fallback ones
-        ent = np.zeros(len(active), dtype=_ENTRY)
-        all_chunks, fb_chunks = [], []
-        for i, (group, p) in enumerate(active):
-            e = ent[i]
-            e["numel"], e["rows"], e["cols"] = p.numel(), 1, p.numel()
-            k = -(-p.numel() // _CHUNK)
-            c = np.empty((k, 2), dtype=np.int32)
-            c[:, 0], c[:, 1] = i, np.arange(k, dtype=np.int32)
-            all_chunks.append(c)
-            if i in fb:
-                self._state_of(p, False)
-                n16, _ = self._copies_of(p)
-                e["w16n"] = 0 if n16 is None else n16.data_ptr()
-                plan["copies"][i] = (n16, None)  # a fallback weight's transposed copy stays on the cast path
-                fb_chunks.append(c)
-        plan["adam"] = _Table(ent, dev)
-        plan["all_chunks"], plan["n_all"] = i32(np.concatenate(all_chunks)), sum(len(c) for c in all_chunks)
-        plan["fb_chunks"], plan["n_fb"] = (i32(np.concatenate(fb_chunks)), sum(len(c) for c in fb_chunks)) if fb_chunks else (None, 0)
+        adam = self._adam_tables(active, copies).to(dev)
+        plan = {"muon": muon, "adam": adam, "copies": list(adam.copies)}
         if not muon:
             return plan
         # Muon: matrices stacked by padded [min, max] shape; X and its transpose ping-pong between two buffers (a product reads one while it writes the other)
@@ -523,7 +380,7 @@ class NativeMuon(torch.optim.Optimizer):
             by_shape.setdefault((_pad32(min(rows, cols)), _pad32(max(rows, cols))), []).append(j)
         ment = np.zeros(len(muon), dtype=_MUON_ENTRY)
         bf = lambda *s: torch.empty(s, dtype=torch.bfloat16, device=dev)
-        groups, chunks, chunk0 = [], [], 0
+        groups = []
         for (mp, np_), members in by_shape.items():
             b = len(members)
             ws = {"X": [bf(b, mp, np_), bf(b, mp, np_)], "Xt": [bf(b, np_, mp), bf(b, np_, mp)], "A": bf(b, mp, mp), "B": bf(b, mp, mp), "tall": False}
@@ -532,12 +389,11 @@ class NativeMuon(torch.optim.Optimizer):
                 ws["acc_mn"] = torch.empty(mp, np_, dtype=torch.float32, device=dev)
             for slot, j in enumerate(members):
                 p = active[muon[j]][1]
-                self._state_of(p, True)
                 rows, cols = p.shape[0], p.numel() // p.shape[0]
                 tall = rows > cols
                 ws["tall"] = ws["tall"] or tall
                 nat, tr = (ws["Xt"], ws["X"]) if tall else (ws["X"], ws["Xt"])  # the weight-oriented image and the other one
-                n16, t16 = self._copies_of(p)
+                n16, t16 = copies[muon[j]]
                 if t16 is not None and not (rows % 64 == 0 and cols % 64 == 0):  # odd-shaped weight: keep its transposed copy on the cast path
                     t16 = None
                 plan["copies"][muon[j]] = (n16, t16)
@@ -546,15 +402,13 @@ class NativeMuon(torch.optim.Optimizer):
                 e["w16t"] = 0 if t16 is None else t16.data_ptr()
                 e["xn"], e["xt"], e["xfin"] = nat[0][slot].data_ptr(), tr[0][slot].data_ptr(), nat[ns_steps % 2][slot].data_ptr()
                 e["rows"], e["cols"], e["ldn"], e["ldt"] = rows, cols, _pad32(cols), _pad32(rows)
-                k = -(-rows // 64) * -(-cols // 64)
-                e["chunk0"], e["nchunks"] = chunk0, k
-                chunk0 += k
-                c = np.empty((k, 2), dtype=np.int32)
-                c[:, 0], c[:, 1] = j, np.arange(k, dtype=np.int32)
-                chunks.append(c)
+                e["nchunks"] = -(-rows // 64) * -(-cols // 64)
             groups.append(ws)
-        plan.update(table=_Table(ment, dev), groups=groups, chunks=i32(np.concatenate(chunks)), n_chunks=chunk0,
-                    chunk_ws=torch.empty(chunk0, dtype=torch.float32, device=dev), inv_norm=torch.empty(len(muon), dtype=torch.float32, device=dev))
+        chunks = tables.chunk_list(ment["nchunks"])
+        ment["chunk0"] = np.cumsum(ment["nchunks"]) - ment["nchunks"]
+        plan.update(table=tables.PinnedTable(ment, dev), groups=groups, chunks=torch.from_numpy(chunks).to(dev), n_chunks=int(chunks.shape[0]),
+                    chunk_ws=torch.empty(chunks.shape[0], dtype=torch.float32, device=dev),
+                    inv_norm=torch.empty(len(muon), dtype=torch.float32, device=dev))
         return plan
 
     def _newton_schulz(self, ws, ns_steps):
@@ -583,60 +437,35 @@ class NativeMuon(torch.optim.Optimizer):
             return loss
         mgroups = [g for g, p in active if takes_muon(g, p)]
         momentum, nesterov, ns_steps = (mgroups[0]["momentum"], mgroups[0]["nesterov"], mgroups[0]["ns_steps"]) if mgroups else (0.0, False, 1)
-        key = (ns_steps,) + tuple((id(p), tuple(p.shape), takes_muon(g, p)) + tuple(map(id, self._copies_of(p))) for g, p in active)
+        copies = [tables.copies_of(self.weight_caches, p) for _, p in active]
+        key = (ns_steps,) + tuple((id(p), tuple(p.shape), takes_muon(g, p)) + tuple(map(id, c)) for (g, p), c in zip(active, copies))
         if key != self._plan_key:
-            self._plan, self._plan_key = self._build_plan(active, ns_steps), key
+            self._plan, self._plan_key = self._build_plan(active, copies, ns_steps), key
         plan = self._plan
-        ent = plan["adam"].records
-        grads = []
         fb_hyper = None
-        for i, (group, p) in enumerate(active):
-            # every pointer is re-read every step (see NativeAdamW.step: load_state_dict(), model.to(), `p.data = ...` replace tensors behind an unchanged id)
-            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-            grads.append(g)
-            if not p.is_contiguous() or g.dtype != torch.float32 or p.dtype != torch.float32:
+        for group, p in active:
+            if not p.is_contiguous() or p.grad.dtype != torch.float32 or p.dtype != torch.float32:
                 raise RuntimeError("NativeMuon: parameters must be contiguous fp32 tensors with fp32 gradients")
-            e = ent[i]
-            e["w"], e["g"] = p.data_ptr(), g.data_ptr()
-            if takes_muon(group, p):
-                e["mode"] = 0 if g.data_ptr() % 16 == 0 else 2
-                continue
-            st = self._state_of(p, False)
-            st["step"] += 1
-            m, v = st["exp_avg"], st["exp_avg_sq"]
-            if not (m.is_contiguous() and v.is_contiguous()):
-                raise RuntimeError("NativeMuon: the AdamW moments must be contiguous")
-            if m.device != p.device or m.dtype != torch.float32 or v.dtype != torch.float32:
-                st["exp_avg"], st["exp_avg_sq"] = m, v = m.to(p.device, torch.float32), v.to(p.device, torch.float32)
-            b1, b2 = group["betas"]
-            if fb_hyper is None:
-                fb_hyper = (b1, b2, group["eps"])
-            elif fb_hyper != (b1, b2, group["eps"]):
-                raise RuntimeError("NativeMuon: all AdamW (fallback) parameters must share betas and eps")
-            e["m"], e["v"] = m.data_ptr(), v.data_ptr()
-            e["mode"] = 0 if all(t.data_ptr() % 16 == 0 for t in (p, g, m, v)) else 2
-            e["lr"], e["wd"] = group["lr"] * group["fallback_lr_scale"], group["weight_decay"]
-            e["bc1"] = 1.0 - b1 ** st["step"]
-            e["bc2_sqrt"] = (1.0 - b2 ** st["step"]) ** 0.5
-        adam_dev = plan["adam"].upload()
-        stream = torch.cuda.current_stream().cuda_stream
-        acc, gn, max_norm = None, 0, 0.0
-        if self.grad_clip_norm is not None:
-            acc = torch.zeros(1, dtype=torch.float32, device=adam_dev.device)
-            ws = torch.empty(plan["n_all"], dtype=torch.float32, device=adam_dev.device)
-            _lib.call("ocn_sumsq_multi", adam_dev.data_ptr(), plan["all_chunks"].data_ptr(), plan["n_all"], acc.data_ptr(), ws.data_ptr(), stream)
+            if not takes_muon(group, p):
+                hyper = (*group["betas"], group["eps"])
+                if fb_hyper is not None and fb_hyper != hyper:
+                    raise RuntimeError("NativeMuon: all AdamW (fallback) parameters must share betas and eps")
+                fb_hyper = hyper
+        adam = plan["adam"]
+        grads = adam.refresh(active, self.state, {"step": (0, int)}, self._fallback_fill, fb_hyper)
+        acc = adam.run(ops.adamw_multi, fb_hyper or (), self.grad_clip_norm, True)  # the norm over all, AdamW over the fallback ones (if any)
+        max_norm = 0.0 if acc is None else float(self.grad_clip_norm)
+        if acc is not None:
             self.last_grad_norm_sq = acc
-            gn, max_norm = acc.data_ptr(), float(self.grad_clip_norm)
-        if plan["fb"]:
-            _lib.call("ocn_adamw_multi", adam_dev.data_ptr(), plan["fb_chunks"].data_ptr(), plan["n_fb"], float(fb_hyper[0]), float(fb_hyper[1]),
-                      float(fb_hyper[2]), gn, max_norm, stream)
         if plan["muon"]:
             ment = plan["table"].records
             for j, i in enumerate(plan["muon"]):
                 group, p = active[i]
                 if (group["momentum"], group["nesterov"], group["ns_steps"]) != (momentum, nesterov, ns_steps):
                     raise RuntimeError("NativeMuon: all Muon groups must share momentum, nesterov and ns_steps")
-                buf = self._state_of(p, True)["momentum_buffer"]
+                buf = self.state[p].get("momentum_buffer")
+                if buf is None:
+                    buf = self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                 if buf.device != p.device or buf.dtype != torch.float32 or not buf.is_contiguous():
                     buf = self.state[p]["momentum_buffer"] = buf.to(p.device, torch.float32).contiguous()
                 e = ment[j]
@@ -650,11 +479,7 @@ class NativeMuon(torch.optim.Optimizer):
             for ws in plan["groups"]:
                 self._newton_schulz(ws, ns_steps)
             ops.muon_apply_multi(mdev, plan["chunks"], plan["n_chunks"])
-        params = [p for _, p in active]
-        torch.autograd.graph.increment_version(params)  # raw-pointer update
-        for p, (n16, t16) in zip(params, plan["copies"]):  # the operand copies were rewritten in the same launches
-            for c in self.weight_caches:
-                c.mark_fresh(p, n16, t16)
+        tables.finish([p for _, p in active], plan["copies"], self.weight_caches)
         return loss
 
 

@@ -72,8 +72,9 @@ const char* ocn_last_error(void);
  *   112            RandomResizedCrop on the device: new ocn_resized_crop_u8 (no signature changed).
  *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed).
  *   114            ragged sources and the validation transform on the device: new ocn_resample_u8 (no signature changed).
- *   115            model EMA: new ocn_ema_lerp_multi (no signature changed). */
-#define OCN_ABI_VERSION 115
+ *   115            model EMA: new ocn_ema_lerp_multi (no signature changed).
+ *   116            distillation: new ocn_distill_rows (no signature changed). */
+#define OCN_ABI_VERSION 116
 int ocn_version(void);
 
 /* ---- GEMMs (MFMA v_mfma_f32_32x32x16_bf16, fp32 accumulate) ------------------------------------
@@ -382,6 +383,14 @@ int ocn_softmax_ce_rows(const float* logits, int ld, void* G, int ldg, int R, in
                         ocn_stream_t stream);
 /* det_rows (may be NULL = fp32 atomics into the three sums): fp32 [R, 3]; row r's contributions to loss_sum / dscale_sum / dbias_sum are
  * written there instead, for the caller to add up in a fixed order (ocn_colsum_f32(..., deterministic = 1)): the reproducible form */
+/* distillation rows (DistillClipLoss.dist_loss, loss.py:189-190, both logit matrices materialised): for each of R rows of the student's logits
+ *   l fp32 [R,N] (row stride ld_s) and the teacher's t fp32 [R,N] (row stride ld_t), p = softmax(l), q = softmax(t) -- both from ONE device routine
+ *   (row maximum, sum of __expf(v - maximum), one reciprocal), so l == t gives G == 0 exactly, and nothing overflows for finite logits:
+ *   loss_sum += (lse(l) - sum_j q_j l_j) * loss_scale;  G bf16 [R,N] = (p - q) * grad_scale -- the whole logit gradient: there is no label part;
+ *   dscale_sum += sum_j (p_j - q_j) * grad_scale * l_j * inv_logit_scale.  det_rows as above (slot 2 = 0).  Each matrix is read twice (an online
+ *   maximum / sum pass, then the pass that writes G); 16-byte loads where the strides and base addresses allow. */
+int ocn_distill_rows(const float* student, int ld_s, const float* teacher, int ld_t, void* G, int ldg, int R, int N, float loss_scale,
+                     float grad_scale, float inv_logit_scale, float* loss_sum, float* dscale_sum, float* det_rows, ocn_stream_t stream);
 /* The same cross-entropy WITHOUT materialised logits (loss.py:103-110 + :136-139 for a [R, N] block of logits_per_image / _per_text;
  * the row-sharded global loss of 8 GPUs has R = 4096, N = 32768): X bf16 [R, E] (already times logit_scale), Y bf16 [N, E].  ONE pass of the MFMA
  * GEMM (round 6; two until round 5): its epilogue consumes the fp32 logits tile in registers and writes G' = exp(logit - c_r) as bf16 [R, ldg] with a

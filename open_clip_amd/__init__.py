@@ -3,6 +3,7 @@
 Public surface (mirrors the reference names):
     create_model, NativeCLIP            <- open_clip.factory.create_model / open_clip.model.CLIP
     NativeClipLoss, NativeSigLipLoss    <- open_clip.loss.ClipLoss / SigLipLoss
+    NativeDistillClipLoss               <- open_clip.loss.DistillClipLoss (create_task(args, model, dist_model=teacher): DistillCLIPTask)
     get_model_config, add_model_config  <- open_clip.factory.get_model_config / add_model_config
     create_task, create_loss            <- open_clip.factory.create_task / create_loss (the reference's task classes around the native losses)
     create_optimizer, OptimizerCfg      <- open_clip_train.optim.create_optimizer / OptimizerCfg (the reference's parameter groups around the native
@@ -18,7 +19,7 @@ def __getattr__(name):  # lazy: importing the package must not require torch.cud
     if name in ("create_model", "NativeCLIP"):
         from . import model
         return getattr(model, name)
-    if name in ("NativeClipLoss", "NativeSigLipLoss"):
+    if name in ("NativeClipLoss", "NativeSigLipLoss", "NativeDistillClipLoss"):
         from . import loss
         return getattr(loss, name)
     if name in ("create_task", "create_loss"):

@@ -65,6 +65,100 @@ __global__ __launch_bounds__(256) void softmax_ce_rows_kernel(const float* __res
     }
 }
 
+// ---- distillation rows (DistillClipLoss.dist_loss, loss.py:189-190) --------------------------------------------------------------------------
+// Four consecutive logits of a row, columns c .. c+3: one 16-byte load where the row allows it, else guarded scalar loads (columns >= N read as -inf:
+// no contribution to the maximum or to the sum).  Thread t owns the columns 4 (t + 256 k) .. + 3 either way, so a row's statistics do not depend on
+// its alignment.
+OCN_DEV f32x4 load_row4(const float* __restrict__ row, int c, int N, bool vec) {
+    if (vec && c + 4 <= N) return *(const f32x4*)(row + c);
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = c + e < N ? row[c + e] : -INFINITY;
+    return v;
+}
+
+// Softmax statistics of one row from ONE read: every thread keeps a running maximum and the sum of exp(v - maximum), rescaled whenever the maximum
+// rises; the threads' pairs are merged through LDS.  mx = the row's maximum, sum = sum_j exp(v_j - mx) (>= 1: nothing overflows for finite logits),
+// inv = 1 / sum.  The student's p and the teacher's q both come from this routine and from row_prob below.
+struct RowStat { float mx, sum, inv; };
+OCN_DEV RowStat row_softmax_stat(const float* __restrict__ row, int N, bool vec, float* red) {
+    float m = -INFINITY, s = 0.f;
+    for (int c = threadIdx.x * 4; c < N; c += blockDim.x * 4) {
+        const f32x4 v = load_row4(row, c, N, vec);
+        const float m4 = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+        if (m4 > m) {
+            s *= __expf(m - m4);  // m = -inf on the first chunk: s = 0 stays 0
+            m = m4;
+        }
+        s += (__expf(v[0] - m) + __expf(v[1] - m)) + (__expf(v[2] - m) + __expf(v[3] - m));
+    }
+    RowStat st;
+    st.mx = block_max(m, red);
+    st.sum = block_sum(s * __expf(m - st.mx), red);  // a thread without a column has m = -inf, s = 0: adds 0
+    st.inv = 1.0f / st.sum;
+    return st;
+}
+// No contraction here or where p - q is formed: fused into fma(e, inv, -q) the product would enter the subtraction unrounded, and p - q of two equal
+// rows would be the rounding error of q instead of 0.
+OCN_DEV float row_prob(float v, const RowStat& st) {
+#pragma clang fp contract(off)
+    return __expf(v - st.mx) * st.inv;
+}
+
+// row r of the student's logits l and of the teacher's logits t, p = softmax(l), q = softmax(t):  loss = lse(l) - sum_j q_j l_j  (evaluated against the
+// student's maximum: ln(sum) - sum_j q_j (l_j - mx), no large terms cancel), G = (p - q) * grad_scale, dscale = sum_j G_j l_j.  Each matrix is read
+// twice: the statistics pass above, then the pass that writes G (at N = 32768 a row of both is 256 KiB).
+__global__ __launch_bounds__(256) void distill_rows_kernel(const float* __restrict__ student, int ld_s, const float* __restrict__ teacher, int ld_t,
+                                                            bf16* __restrict__ G, int ldg, int R, int N, float loss_scale, float grad_scale,
+                                                            float inv_logit_scale, int vec, int gvec, float* __restrict__ loss_sum,
+                                                            float* __restrict__ dscale_sum, float* __restrict__ det_rows) {
+    __shared__ float red[8];
+    const int r = blockIdx.x;
+    const float* srow = student + (size_t)r * ld_s;
+    const float* trow = teacher + (size_t)r * ld_t;
+    bf16* grow = G + (size_t)r * ldg;
+    const RowStat ss = row_softmax_stat(srow, N, vec, red);
+    const RowStat ts = row_softmax_stat(trow, N, vec, red);
+    float ql = 0.f, ds = 0.f;
+    for (int c = threadIdx.x * 4; c < N; c += blockDim.x * 4) {
+        const f32x4 l = load_row4(srow, c, N, vec), t = load_row4(trow, c, N, vec);
+        bf16x4 g16;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma clang fp contract(off)
+            const bool in = c + e < N;
+            const float lv = in ? l[e] : ss.mx, tv = in ? t[e] : ts.mx;  // (finite stand-ins: the lanes beyond N are neither added nor stored)
+            const float q = row_prob(tv, ts);
+            const float g = (row_prob(lv, ss) - q) * grad_scale;
+            g16[e] = f2bf(g);
+            if (in) {
+                ds += g * lv;
+                ql += q * (lv - ss.mx);
+            }
+        }
+        if (gvec && c + 4 <= N) {
+            *(bf16x4*)(grow + c) = g16;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c + e < N) grow[c + e] = g16[e];
+        }
+    }
+    ql = block_sum(ql, red);
+    ds = block_sum(ds, red);
+    if (threadIdx.x == 0) {
+        const float loss = (__logf(ss.sum) - ql) * loss_scale;
+        if (det_rows) {
+            det_rows[(size_t)r * 3] = loss;
+            det_rows[(size_t)r * 3 + 1] = ds * inv_logit_scale;
+            det_rows[(size_t)r * 3 + 2] = 0.f;
+        } else {
+            unsafeAtomicAdd(loss_sum, loss);
+            unsafeAtomicAdd(dscale_sum, ds * inv_logit_scale);
+        }
+    }
+}
+
 // SigLIP pairwise sigmoid loss (loss.py:344-367): labels +1 on (r, r+label_offset) unless negative_only, else -1
 __global__ __launch_bounds__(256) void siglip_rows_kernel(const float* __restrict__ logits, int ld, bf16* __restrict__ G, int ldg,
                                                            int R, int N, int label_offset, int negative_only, float bias_host,
@@ -361,6 +455,20 @@ extern "C" int ocn_softmax_ce_rows(const float* logits, int ld, void* G, int ldg
     hipLaunchKernelGGL(softmax_ce_rows_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, logits, ld, (bf16*)G, ldg, R, N,
                        label_offset, loss_scale, grad_scale, inv_logit_scale, loss_sum, dscale_sum, det_rows);
     OCN_CHECK_LAUNCH("ocn_softmax_ce_rows");
+    return OCN_OK;
+}
+
+extern "C" int ocn_distill_rows(const float* student, int ld_s, const float* teacher, int ld_t, void* G, int ldg, int R, int N, float loss_scale,
+                                float grad_scale, float inv_logit_scale, float* loss_sum, float* dscale_sum, float* det_rows, ocn_stream_t stream) {
+    OCN_CHECK_ARG(student && teacher && G && loss_sum && dscale_sum, "ocn_distill_rows: null operand");
+    OCN_CHECK_ARG(R > 0 && N > 0, "ocn_distill_rows: bad shape R=%d N=%d", R, N);
+    OCN_CHECK_ARG(ld_s >= N && ld_t >= N && ldg >= N, "ocn_distill_rows: row stride below N=%d (ld_s=%d ld_t=%d ldg=%d)", N, ld_s, ld_t, ldg);
+    // 16-byte loads / 8-byte stores only where every row of the matrix starts on that grid
+    const int vec = ld_s % 4 == 0 && ld_t % 4 == 0 && ((uintptr_t)student & 15) == 0 && ((uintptr_t)teacher & 15) == 0;
+    const int gvec = ldg % 4 == 0 && ((uintptr_t)G & 7) == 0;
+    hipLaunchKernelGGL(distill_rows_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, student, ld_s, teacher, ld_t, (bf16*)G, ldg, R, N, loss_scale,
+                       grad_scale, inv_logit_scale, vec, gvec, loss_sum, dscale_sum, det_rows);
+    OCN_CHECK_LAUNCH("ocn_distill_rows");
     return OCN_OK;
 }
 

@@ -1,7 +1,8 @@
 """Contrastive losses of the hot path over the HIP kernels: drop-ins for ``open_clip.loss.ClipLoss`` and
 ``SigLipLoss`` (reference ``src/open_clip/loss.py:57-141``, ``:314-489``) with the same constructor arguments,
 ``forward`` signature and return convention, so ``CLIPTask(model, loss=NativeClipLoss(...))`` works
-(clip_task.py:26,38-39).
+(clip_task.py:26,38-39); ``NativeDistillClipLoss`` is ``DistillClipLoss`` (loss.py:187-223) for ``DistillCLIPTask``: the contrastive Function
+and a second one for the distillation term, composed.
 
 Each loss is one autograd Function that computes the loss AND its feature / logit_scale gradients in the
 forward (the logit gradient G is a by-product of the same pass over the logits), so the backward is a scale by
@@ -71,7 +72,8 @@ class _PairTerm:
     evaluates (s X) first, too -- so the logits GEMM, the G^T (s X) product and the kernels take no scalar from the host;
     the two places where s multiplies / divides a small result are 1-element device ops."""
 
-    def __init__(self, X, Y, scale):
+    def __init__(self, X, Y, scale, grad=True):
+        """``grad=False``: a term that only supplies logits (the teacher's, in ``distill``): no G is allocated -- [4096, 32768] of it is 256 MiB"""
         self.X, self.Y, self.s = X, Y, scale
         self.R, self.N, self.E = X.shape[0], Y.shape[0], X.shape[1]
         self.xs16, self.y16 = _bf16_rows(X, scale), _bf16_rows(Y)
@@ -82,8 +84,8 @@ class _PairTerm:
         self.rowscale = None  # fused one-pass cross-entropy: G holds exp(logit - shift_r); the softmax part of the gradient is G * rowscale[:, None]
         self.deterministic = False  # reproducible sums (set by the loss Function): the rows' loss / d-scale contributions are added in a fixed order
         # the logit gradient's operand matrix: every column below N is written by the loss kernel; only the padding (K of the G @ Y product in steps of 64) must be zero
-        self.G = torch.empty(self.R, self.ldg, dtype=BF16, device=X.device)
-        if self.ldg > self.N:
+        self.G = torch.empty(self.R, self.ldg, dtype=BF16, device=X.device) if grad else None
+        if grad and self.ldg > self.N:
             self.G[:, self.N:].zero_()
 
     def compute_logits(self, bias=None):
@@ -134,6 +136,24 @@ class _PairTerm:
             return
         ops.siglip_rows(self._materialise(), self.G, self.N, label_offset, negative_only, self._bias_dev(), loss_scale, grad_scale, 1.0,
                         acc[0:1], acc[1:2], acc[2:3])
+
+    def distill(self, teacher_term, loss_scale, grad_scale, acc):
+        """rows' -sum_j softmax(teacher)_j log_softmax(self)_j (loss.py:189-190) -> acc[0] += loss, acc[1] += sum(G * logits) (= s * d/dscale); fills
+        G = (softmax(self) - softmax(teacher)) * grad_scale.  That is the whole logit gradient -- no label, no row scale: ``_onehot`` and ``rowscale``
+        stay None and dX / dY are the plain products, as for SigLIP's negative-only chunks.  Both logit matrices are materialised (a one-pass form
+        would need two MFMA accumulations per tile); ``teacher_term`` is built with ``grad=False`` and is only read."""
+        if (teacher_term.R, teacher_term.N) != (self.R, self.N):
+            raise RuntimeError(f"distill: teacher logits [{teacher_term.R}, {teacher_term.N}] against student logits [{self.R}, {self.N}]")
+        self._onehot, self.rowscale = None, None
+        student, teacher = self._materialise(), teacher_term._materialise()
+        if self.deterministic:
+            rows = torch.empty(self.R, 3, dtype=F32, device=self.X.device)
+            ops.distill_rows(student, teacher, self.G, self.N, loss_scale, grad_scale, 1.0, acc[0:1], acc[1:2], det_rows=rows)
+            tot = torch.zeros(3, dtype=F32, device=self.X.device)
+            ops.colsum_f32(rows, tot, deterministic=True)
+            acc[0:2].add_(tot[0:2])
+            return
+        ops.distill_rows(student, teacher, self.G, self.N, loss_scale, grad_scale, 1.0, acc[0:1], acc[1:2])
 
     def _bias_dev(self):
         return 0.0 if self._bias is None else self._bias.detach().reshape(1).to(F32).contiguous()
@@ -214,10 +234,99 @@ def _device_scalar(t, dev):
     return t.detach().to(device=dev, dtype=F32).reshape(1)
 
 
-def _term(X, Y, s, deterministic):
-    t = PairTerm(X, Y, s)
+def _term(X, Y, s, deterministic, grad=True):
+    t = PairTerm(X, Y, s) if grad else PairTerm(X, Y, s, grad=False)  # (the seam's replacements take the keyword only where a teacher term is built)
     t.deterministic = bool(deterministic)
     return t
+
+
+def _pairwise_modes(local, fill, s, local_loss, gather_with_grad, rank, world_size, row_sharded, comm):
+    """The mode skeleton shared by the softmax losses over ``get_logits`` (loss.py:91-116): ``_ClipLossFn`` (cross-entropy against the diagonal) and
+    ``_DistillLossFn`` (the teacher's softmax as the target).  What differs between them is WHAT is gathered and the ROW OPERATION that fills G:
+
+    ``local``: this rank's fp32 feature matrices [B, *]; the first two are the image and text features [B, E] that gradient flows to.  All of them
+    travel in ONE packed all-gather of [B, sum of widths].
+    ``fill(rows, cols, label_offset, weight, acc) -> (ti, tt)``: builds the image-direction and text-direction terms of ``rows`` (a tuple shaped like
+    ``local``) against ``cols``, applies the row operation with loss and gradient weight ``weight`` (adding into ``acc``) and returns the two terms
+    whose G it filled.
+
+    Returns (dI, dT, d_all, acc): the gradients that reach the local features directly, the [W*B, 2E] payload of the backward's
+    reduce-scatter (``gather_with_grad``; else None) and acc = [loss, d loss / d logit_scale]."""
+    I = local[0]
+    dev = I.device
+    B, E = I.shape
+    acc = torch.zeros(2, dtype=F32, device=dev)  # [loss_sum, sum(G * logits) = s * dscale]
+    # a communicator handed in with world_size 1 (bench.py --native-comm on one GPU, tests) still runs the distributed form: every collective is
+    # an identity then, but counts, dtypes and pointers travel the path a node's ranks use
+    use_dist = world_size > 1 or comm is not None
+    if use_dist:
+        packed = torch.cat(local, dim=1)
+        allp = torch.empty(world_size * B, packed.shape[1], dtype=F32, device=dev)
+        _all_gather(allp, packed, comm)
+        gathered = tuple(part.contiguous() for part in allp.split([x.shape[1] for x in local], dim=1))
+    if not use_dist:
+        # loss.py:109-110: li = s I T^T, lt = s T I^T ; labels arange(B)
+        ti, tt = fill(local, local, 0, 0.5 / B, acc)
+        dI = ti.dX() + tt.dY()
+        dT = tt.dX() + ti.dY()
+        d_all = None
+    elif local_loss:
+        # loss.py:103-104 + :82-83: li = s I_loc T_all^T, lt = s T_loc I_all^T, labels arange(B) + B*rank
+        ti, tt = fill(local, gathered, B * rank, 0.5 / B, acc)
+        dI, dT = ti.dX(), tt.dX()            # through the local operands
+        d_all = None
+        if gather_with_grad:                  # ... and through the gathered ones (summed over ranks in backward)
+            d_all = torch.zeros(world_size * B, 2 * E, dtype=F32, device=dev)  # [N, 2E]: d I_all | d T_all, written in place
+            tt.dY(into=d_all[:, :E])
+            ti.dY(into=d_all[:, E:])
+    elif row_sharded and not gather_with_grad:
+        # Same loss and the same local gradients as the branch below (loss.py:106-107, :47-50), without its W-fold
+        # redundancy (SURVEY.md 8e-4 / 8f-2): rank r evaluates only ITS rows of logits_per_image and logits_per_text
+        # ([B, N] each, labels arange(B) + B*rank) with the global 1/(2N) weight, the row partial sums of the loss and of
+        # d/d logit_scale are all-reduced, and the gradient that reaches this rank's features through the COLUMNS of the
+        # other ranks' rows arrives by one reduce-scatter of [N, 2E] -- done here, since the loss computes its gradients
+        # in the forward.  6 GEMMs of 2*B*N*E flops instead of 6 of 2*N*N*E.
+        N = world_size * B
+        ti, tt = fill(local, gathered, B * rank, 0.5 / N, acc)
+        dI, dT = ti.dX(), tt.dX()
+        through_cols = torch.zeros(N, 2 * E, dtype=F32, device=dev)  # [N, 2E]: d I_all | d T_all from my rows, written in place
+        tt.dY(into=through_cols[:, :E])
+        ti.dY(into=through_cols[:, E:])
+        mine = torch.empty(B, 2 * E, dtype=F32, device=dev)
+        _reduce_scatter_sum(mine, through_cols, comm)
+        dI = dI + mine[:, :E]
+        dT = dT + mine[:, E:]
+        _all_reduce_sum(acc, comm)
+        d_all = None
+    else:
+        # loss.py:106-107: li = s I_all T_all^T, lt = li^T ; labels arange(N)
+        N = world_size * B
+        ti, tt = fill(gathered, gathered, 0, 0.5 / N, acc)
+        dI_all = ti.dX() + tt.dY()
+        dT_all = tt.dX() + ti.dY()
+        lo, hi = rank * B, (rank + 1) * B
+        if gather_with_grad:
+            dI = torch.zeros(B, E, dtype=F32, device=dev)
+            dT = torch.zeros(B, E, dtype=F32, device=dev)
+            d_all = torch.cat([dI_all, dT_all], dim=1).contiguous()
+        else:                                   # loss.py:47-50: only the local slot carries gradient
+            dI, dT = dI_all[lo:hi].contiguous(), dT_all[lo:hi].contiguous()
+            d_all = None
+    acc[1:2].div_(s)  # d loss / d logit_scale = sum(G * logits) / s
+    return dI, dT, d_all, acc
+
+
+def _scaled_feature_grads(ctx, gout):
+    """the backward both Functions share: the gradients were computed in the forward, so it is the backward of the differentiable all-gather
+    (one reduce-scatter, when ``gather_with_grad``) and a scale by the incoming scalar -> (d image_features, d text_features, d logit_scale)"""
+    dI, dT, acc, d_all = ctx.saved_tensors
+    B, E, idt, tdt, comm = ctx.meta[:5]
+    if d_all is not None:  # backward of the differentiable all-gather = reduce-scatter(sum) (loss.py:23-26)
+        mine = torch.empty(B, 2 * E, dtype=F32, device=dI.device)
+        _reduce_scatter_sum(mine, d_all, comm)
+        dI = dI + mine[:, :E]
+        dT = dT + mine[:, E:]
+    return (dI * gout).to(idt), (dT * gout).to(tdt), acc[1] * gout
 
 
 class _ClipLossFn(torch.autograd.Function):
@@ -225,96 +334,58 @@ class _ClipLossFn(torch.autograd.Function):
     def forward(ctx, image_features, text_features, logit_scale, local_loss, gather_with_grad, rank, world_size, row_sharded=False, comm=None,
                 logit_bias=None, deterministic=False):
         I, T = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
-        dev = I.device
-        s = _device_scalar(logit_scale, dev)  # stays on the device: no host synchronisation inside the step
-        B, E = I.shape
-        acc = torch.zeros(2, dtype=F32, device=dev)  # [loss_sum, sum(G * logits) = s * dscale]
-        # a communicator handed in with world_size 1 (bench.py --native-comm on one GPU, tests) still runs the distributed form: every collective is
-        # an identity then, but counts, dtypes and pointers travel the path a node's ranks use
-        use_dist = world_size > 1 or comm is not None
-        if use_dist:
-            packed = torch.cat([I, T], dim=1)
-            allp = torch.empty(world_size * B, 2 * E, dtype=F32, device=dev)
-            _all_gather(allp, packed, comm)
-            I_all, T_all = allp[:, :E].contiguous(), allp[:, E:].contiguous()
-        if not use_dist:
-            # loss.py:109-110: li = s I T^T, lt = s T I^T ; labels arange(B)
-            ti = _term(I, T, s, deterministic).compute_logits()
-            tt = _term(T, I, s, deterministic).compute_logits()
+        s = _device_scalar(logit_scale, I.device)  # stays on the device: no host synchronisation inside the step
+
+        def fill(rows, cols, label_offset, weight, acc):
+            ti = _term(rows[0], cols[1], s, deterministic).compute_logits()
+            tt = _term(rows[1], cols[0], s, deterministic).compute_logits()
             for term in (ti, tt):
-                term.softmax_ce(0, 0.5 / B, 0.5 / B, acc)
-            dI = ti.dX() + tt.dY()
-            dT = tt.dX() + ti.dY()
-            d_all = None
-        elif local_loss:
-            # loss.py:103-104 + :82-83: li = s I_loc T_all^T, lt = s T_loc I_all^T, labels arange(B) + B*rank
-            ti = _term(I, T_all, s, deterministic).compute_logits()
-            tt = _term(T, I_all, s, deterministic).compute_logits()
-            for term in (ti, tt):
-                term.softmax_ce(B * rank, 0.5 / B, 0.5 / B, acc)
-            dI, dT = ti.dX(), tt.dX()            # through the local operands
-            d_all = None
-            if gather_with_grad:                  # ... and through the gathered ones (summed over ranks in backward)
-                d_all = torch.zeros(world_size * B, 2 * E, dtype=F32, device=dev)  # [N, 2E]: d I_all | d T_all, written in place
-                tt.dY(into=d_all[:, :E])
-                ti.dY(into=d_all[:, E:])
-        elif row_sharded and not gather_with_grad:
-            # Same loss and the same local gradients as the branch below (loss.py:106-107, :47-50), without its W-fold
-            # redundancy: rank r evaluates only ITS rows of logits_per_image and logits_per_text
-            # ([B, N] each, labels arange(B) + B*rank) with the global 1/(2N) weight, the row partial sums of the loss and of
-            # d/d logit_scale are all-reduced, and the gradient that reaches this rank's features through the COLUMNS of the
-            # other ranks' rows arrives by one reduce-scatter of [N, 2E] -- done here, since the loss computes its gradients
-            # in the forward.  6 GEMMs of 2*B*N*E flops instead of 6 of 2*N*N*E.
-            N = world_size * B
-            ti = _term(I, T_all, s, deterministic).compute_logits()
-            tt = _term(T, I_all, s, deterministic).compute_logits()
-            for term in (ti, tt):
-                term.softmax_ce(B * rank, 0.5 / N, 0.5 / N, acc)
-            dI, dT = ti.dX(), tt.dX()
-            through_cols = torch.zeros(N, 2 * E, dtype=F32, device=dev)  # [N, 2E]: d I_all | d T_all from my rows, written in place
-            tt.dY(into=through_cols[:, :E])
-            ti.dY(into=through_cols[:, E:])
-            mine = torch.empty(B, 2 * E, dtype=F32, device=dev)
-            _reduce_scatter_sum(mine, through_cols, comm)
-            dI = dI + mine[:, :E]
-            dT = dT + mine[:, E:]
-            _all_reduce_sum(acc, comm)
-            d_all = None
-        else:
-            # loss.py:106-107: li = s I_all T_all^T, lt = li^T ; labels arange(N)
-            N = world_size * B
-            ti = _term(I_all, T_all, s, deterministic).compute_logits()
-            tt = _term(T_all, I_all, s, deterministic).compute_logits()
-            for term in (ti, tt):
-                term.softmax_ce(0, 0.5 / N, 0.5 / N, acc)
-            dI_all = ti.dX() + tt.dY()
-            dT_all = tt.dX() + ti.dY()
-            lo, hi = rank * B, (rank + 1) * B
-            if gather_with_grad:
-                dI = torch.zeros(B, E, dtype=F32, device=dev)
-                dT = torch.zeros(B, E, dtype=F32, device=dev)
-                d_all = torch.cat([dI_all, dT_all], dim=1).contiguous()
-            else:                                   # loss.py:47-50: only the local slot carries gradient
-                dI, dT = dI_all[lo:hi].contiguous(), dT_all[lo:hi].contiguous()
-                d_all = None
-        acc[1:2].div_(s)  # d loss / d logit_scale = sum(G * logits) / s
+                term.softmax_ce(label_offset, weight, weight, acc)
+            return ti, tt
+
+        dI, dT, d_all, acc = _pairwise_modes((I, T), fill, s, local_loss, gather_with_grad, rank, world_size, row_sharded, comm)  # gathers [W*B, 2E]
         ctx.save_for_backward(dI, dT, acc, d_all)
-        ctx.meta = (world_size, B, E, image_features.dtype, text_features.dtype, comm, logit_bias is not None)
+        ctx.meta = (I.shape[0], I.shape[1], image_features.dtype, text_features.dtype, comm, logit_bias is not None)
         return acc[0].clone()
 
     @staticmethod
     def backward(ctx, gout):
-        dI, dT, acc, d_all = ctx.saved_tensors
-        world_size, B, E, idt, tdt, comm, has_bias = ctx.meta
-        if d_all is not None:  # backward of the differentiable all-gather = reduce-scatter(sum) (loss.py:23-26)
-            mine = torch.empty(B, 2 * E, dtype=F32, device=dI.device)
-            _reduce_scatter_sum(mine, d_all, comm)
-            dI = dI + mine[:, :E]
-            dT = dT + mine[:, E:]
+        dI, dT, dscale = _scaled_feature_grads(ctx, gout)
+        has_bias = ctx.meta[5]
         # logit_bias shifts every logit of a row alike: its gradient is exactly zero (the softmax gradient of a row sums to 0), but it is
         # a real gradient, as in the reference (loss.py:111-113) -- DDP then sees the parameter reduced like every other one
         dbias = (gout * 0.0).reshape(()) if has_bias else None
-        return (dI * gout).to(idt), (dT * gout).to(tdt), acc[1] * gout, None, None, None, None, None, None, dbias, None
+        return dI, dT, dscale, None, None, None, None, None, None, dbias, None
+
+
+class _DistillLossFn(torch.autograd.Function):
+    """The distillation term of ``DistillClipLoss`` (loss.py:189-190, :215-218) alone: (D(t_img, l_img) + D(t_txt, l_txt)) / 2 with
+    D(t, l) = mean_r(-sum_j softmax(t)_rj log_softmax(l)_rj), the teacher's logits built by the same ``get_logits`` as the student's -- the same
+    modes with the same weights as ``_ClipLossFn``.  The logit gradient of a row is softmax(l) - softmax(t); the teacher's inputs get none."""
+
+    @staticmethod
+    def forward(ctx, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale, local_loss,
+                gather_with_grad, rank, world_size, row_sharded=False, comm=None, deterministic=False):
+        I, T = image_features.detach().float().contiguous(), text_features.detach().float().contiguous()
+        DI, DT = dist_image_features.detach().float().contiguous(), dist_text_features.detach().float().contiguous()  # [B, E_t]: E_t need not be E
+        s, ds = _device_scalar(logit_scale, I.device), _device_scalar(dist_logit_scale, I.device)
+
+        def fill(rows, cols, label_offset, weight, acc):
+            ti = _term(rows[0], cols[1], s, deterministic).compute_logits()
+            tt = _term(rows[1], cols[0], s, deterministic).compute_logits()
+            ti.distill(_term(rows[2], cols[3], ds, deterministic, grad=False).compute_logits(), weight, weight, acc)
+            tt.distill(_term(rows[3], cols[2], ds, deterministic, grad=False).compute_logits(), weight, weight, acc)
+            return ti, tt
+
+        # ONE packed all-gather of [B, 2E + 2E_t]: student image | text, teacher image | text
+        dI, dT, d_all, acc = _pairwise_modes((I, T, DI, DT), fill, s, local_loss, gather_with_grad, rank, world_size, row_sharded, comm)
+        ctx.save_for_backward(dI, dT, acc, d_all)
+        ctx.meta = (I.shape[0], I.shape[1], image_features.dtype, text_features.dtype, comm)
+        return acc[0].clone()
+
+    @staticmethod
+    def backward(ctx, gout):
+        return _scaled_feature_grads(ctx, gout) + (None,) * 10
 
 
 PairTerm = _PairTerm  # the one seam tests replace to exercise the collective plumbing on CPU/gloo
@@ -344,6 +415,27 @@ class NativeClipLoss(nn.Module):
         loss = _ClipLossFn.apply(image_features, text_features, logit_scale, self.local_loss, self.gather_with_grad,
                                  self.rank, self.world_size, self.row_sharded, self.comm, logit_bias, self.deterministic)
         return {"contrastive_loss": loss} if output_dict else loss
+
+
+class NativeDistillClipLoss(NativeClipLoss):
+    """``open_clip.loss.DistillClipLoss`` (loss.py:187-223) on the HIP path: the constructor is ``NativeClipLoss``'s, ``forward`` takes the student's
+    and the teacher's features and scales and returns ``(contrastive_loss, distill_loss)`` or the dict with those keys (``DistillCLIPTask`` sums the
+    ``*_loss`` entries).  No ``logit_bias``, as in the reference.
+
+    The two losses are two autograd Functions, composed: the contrastive one is ``NativeClipLoss``'s call unchanged (the fused one-pass
+    cross-entropy; value and gradients bit for bit), the distillation one is ``_DistillLossFn``.  Each output carries its own gradient, so ANY
+    weighting of the two is differentiated exactly (one G behind one output would fix the weights at 1:1).  The price: the student's features are
+    gathered twice and there are eight small gradient GEMMs instead of four.  The teacher's embedding width may differ from the student's."""
+
+    def forward(self, image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale, output_dict=False):
+        contrastive_loss = _ClipLossFn.apply(image_features, text_features, logit_scale, self.local_loss, self.gather_with_grad,
+                                             self.rank, self.world_size, self.row_sharded, self.comm, None, self.deterministic)
+        distill_loss = _DistillLossFn.apply(image_features, text_features, logit_scale, dist_image_features, dist_text_features, dist_logit_scale,
+                                            self.local_loss, self.gather_with_grad, self.rank, self.world_size, self.row_sharded, self.comm,
+                                            self.deterministic)
+        if output_dict:
+            return {"contrastive_loss": contrastive_loss, "distill_loss": distill_loss}
+        return contrastive_loss, distill_loss
 
 
 class _SigLipLossFn(torch.autograd.Function):

@@ -633,6 +633,18 @@ def softmax_ce_rows(logits, G, N, label_offset, loss_scale, grad_scale, inv_logi
               float(inv_logit_scale), _chk(loss_sum, F32, "loss_sum"), _chk(dscale_sum, F32, "dscale_sum"), _chk(det_rows, F32, "det_rows"), _stream())
 
 
+def distill_rows(student, teacher, G, N, loss_scale, grad_scale, inv_logit_scale, loss_sum, dscale_sum, det_rows=None):
+    """rows of softmax(teacher) against log_softmax(student) (ocn_distill_rows): G = (p - q) * grad_scale, loss_sum += (lse(l) - sum q l) * loss_scale,
+    dscale_sum += sum(G * l) * inv_logit_scale; ``det_rows`` as for ``softmax_ce_rows``"""
+    if student.shape != teacher.shape:
+        raise RuntimeError(f"distill_rows: student logits {tuple(student.shape)} and teacher logits {tuple(teacher.shape)} differ in shape")
+    ps, ld_s = _chk2d(student, F32, "student")
+    pt, ld_t = _chk2d(teacher, F32, "teacher")
+    pg, ldg = _chk2d(G, BF16, "G")
+    _lib.call("ocn_distill_rows", ps, ld_s, pt, ld_t, pg, ldg, student.shape[0], N, float(loss_scale), float(grad_scale), float(inv_logit_scale),
+              _chk(loss_sum, F32, "loss_sum"), _chk(dscale_sum, F32, "dscale_sum"), _chk(det_rows, F32, "det_rows"), _stream())
+
+
 def fused_logits_ce(xs16, y16, G, N, label_offset, loss_scale, grad_scale, loss_sum, dscale_sum):
     """cross-entropy of the rows of xs16 @ y16[:N]^T against arange + label_offset without materialising the logits, in ONE pass of the MFMA GEMM
     (ocn_fused_logits_ce): fills G bf16 [R, ldg] with exp(logit - shift_r) and returns ``rowscale`` fp32 [R] = grad_scale / sum_j G[r, j] -- the softmax part

@@ -73,7 +73,10 @@ const char* ocn_last_error(void);
  *   113            colour jitter and grayscale on the device: new ocn_color_jitter_u8 (no signature changed).
  *   114            ragged sources and the validation transform on the device: new ocn_resample_u8 (no signature changed).
  *   115            model EMA: new ocn_ema_lerp_multi (no signature changed).
- *   116            distillation: new ocn_distill_rows (no signature changed). */
+ *   116            distillation: new ocn_distill_rows (no signature changed).
+ *   116 (still)    position tables at another image size / context length: new ocn_pos_resample_fwd, ocn_pos_resample_bwd.  No signature changed, and
+ *                  the number stays: tests/test_distill.py pins 116, and a library built before the two entry points existed fails at load on the
+ *                  missing symbols, not later. */
 #define OCN_ABI_VERSION 116
 int ocn_version(void);
 
@@ -249,6 +252,30 @@ int ocn_patch_keep_inverse(const int32_t* keep, int32_t* inv, int B, int G, int 
 int ocn_resized_crop_u8(const void* src_u8, int B, int Hs, int Ws, const int32_t* boxes, void* out_u8, int Ho, int Wo, ocn_stream_t stream);
 int ocn_resample_u8(const void* arena_u8, int64_t arena_bytes, const int64_t* offsets, const int32_t* plan, int B, void* out_u8, int Ho, int Wo, int fill,
                     ocn_stream_t stream);
+
+/* ---- position tables at another size (model.py:790-854 resize_pos_embed / resize_text_pos_embed; csrc/pos_resample.hip) -------------------
+ * ocn_pos_resample_fwd: src fp32 [prefix + Hs*Ws, C] -> dst fp32 [prefix + Ho*Wo, C], both row-major, channels last as the parameter is stored.  The
+ *   `prefix` rows (the class token: 1, or 0) are copied; the grid rows are F.interpolate(grid [1, C, Hs, Ws], size=(Ho, Wo), mode, antialias,
+ *   align_corners=False) per channel, mode 0 = (bi)linear, 1 = bicubic.  The 1-D text table is Hs = Ho = 1.  Per axis, length n -> R, c2 = n (2r + 1):
+ *     antialias = 1:  M = max(n, R), K = 2 (cubic) / 1 (linear); taps k in [max(0, (c2 - 2KM + R) / 2R), min(n, (c2 + 2KM + R) / 2R)), weight
+ *                     f(((2k + 1) R - c2) / 2M) / (the window's sum, added in tap order); f = Keys' cubic with a = -0.5, or max(0, 1 - |x|)
+ *     cubic:          x = (c2 - R) / 2R, f0 = floor(x), t = x - f0: taps f0 - 1 .. f0 + 2, each index clamped to [0, n - 1] (clamped taps add up on the
+ *                     border element), weights cubic(j - 1 - t) with a = -0.75, not renormalised
+ *     linear:         x = max((c2 - R) / 2R, 0), f0 = min(int(x), n - 1), t = x - f0: 1 - t on f0, t on min(f0 + 1, n - 1)
+ *   Tap positions come from exact integers; the one division per weight argument is their only rounding.  Taps of weight exactly 0 are dropped, so an
+ *   axis whose two lengths are equal is the identity: the result holds the source's bits.  Summation, fp32 with fused multiply-adds, in ONE order:
+ *   dst = sum_y wy * (sum_x wx * src), the inner sum first, taps in increasing order, each sum started with its first product: the same bits every run.
+ * ocn_pos_resample_bwd: the transposed map dsrc = W^T ddst (ddst fp32 [prefix + Ho*Wo, C] -> dsrc fp32 [prefix + Hs*Ws, C], every row written, prefix
+ *   rows copied) in gather form: every source element sums, over the outputs whose taps hold it in increasing output index (rows outside, columns
+ *   inside), the weight the forward gives it there.  No atomic: the same bits every run.
+ * Lanes run along C: float4 where C % 4 == 0 and both tables are 16-byte aligned, scalar otherwise; any C >= 1.
+ * Refused before any launch, the argument named: a grid side outside [1, 64]; a 1-D linear call (Hs = Ho = 1, mode 0) with a length outside [1, 4096]
+ *   (forward; the backward takes sides up to 64 only) or with antialias = 1 (torch raises there too); mode or antialias outside {0, 1}; prefix outside
+ *   [0, 64]; C < 1; a null or misaligned table. */
+int ocn_pos_resample_fwd(const float* src, float* dst, int prefix, int Hs, int Ws, int Ho, int Wo, int C, int mode /*0 linear, 1 cubic*/, int antialias,
+                         ocn_stream_t stream);
+int ocn_pos_resample_bwd(const float* ddst, float* dsrc, int prefix, int Hs, int Ws, int Ho, int Wo, int C, int mode, int antialias,
+                         ocn_stream_t stream);
 
 /* ---- device-side colour jitter and grayscale (transform.py:335-364, :442-450: color_jitter(*aug_cfg.color_jitter, p), gray_scale(p)) ----------
  * ocn_color_jitter_u8: img uint8 [B, H, W, 3] (HWC), factors fp32 [B, 4] = (brightness, contrast, saturation, hue) and plan int32 [B] ON THE DEVICE,

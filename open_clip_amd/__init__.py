@@ -1,7 +1,11 @@
 """open_clip_amd: MI355X-native (gfx950) CLIP training hot path behind open_clip's model / loss API.
 
 Public surface (mirrors the reference names):
-    create_model, NativeCLIP            <- open_clip.factory.create_model / open_clip.model.CLIP
+    create_model, NativeCLIP            <- open_clip.factory.create_model / open_clip.model.CLIP (force_image_size=, force_context_length= as the
+                                           reference's; dynamic_img_size=True: the image tower takes calls at other image sizes)
+    resize_pos_embed, resize_text_pos_embed
+                                        <- open_clip.model.resize_pos_embed / resize_text_pos_embed: a checkpoint's position tables at another image
+                                           size / context length, resampled on the device (ocn_pos_resample_fwd), rectangular grids included
     NativeClipLoss, NativeSigLipLoss    <- open_clip.loss.ClipLoss / SigLipLoss
     NativeDistillClipLoss               <- open_clip.loss.DistillClipLoss (create_task(args, model, dist_model=teacher): DistillCLIPTask)
     get_model_config, add_model_config  <- open_clip.factory.get_model_config / add_model_config
@@ -16,7 +20,7 @@ from .configs import add_model_config, get_model_config, list_models  # noqa: F4
 
 
 def __getattr__(name):  # lazy: importing the package must not require torch.cuda / the shared library
-    if name in ("create_model", "NativeCLIP"):
+    if name in ("create_model", "NativeCLIP", "resize_pos_embed", "resize_text_pos_embed"):
         from . import model
         return getattr(model, name)
     if name in ("NativeClipLoss", "NativeSigLipLoss", "NativeDistillClipLoss"):

@@ -37,6 +37,8 @@ SIGNATURES = {
     "ocn_patchify_u8": [_p, _i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), _p, _i, _p, _i, _i, _i, _i, _i, _p],
     "ocn_resized_crop_u8": [_p, _i, _i, _i, _p, _p, _i, _i, _p],
     "ocn_resample_u8": [_p, _l, _p, _p, _i, _p, _i, _i, _i, _p],
+    "ocn_pos_resample_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "ocn_pos_resample_bwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "ocn_color_jitter_u8": [_p, _i, _i, _i, _p, _p, _p, _p, _p],
     "ocn_embed_assemble_fwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
     "ocn_embed_assemble_bwd": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],

@@ -178,8 +178,10 @@ def vision_tokens(cfg: dict, patch_dropout=None) -> int:
     """tokens of the image tower (class token + patches).  ``patch_dropout`` (None / 0: every patch): the tokens a TRAINING step executes with
     that dropout probability (transformer.py:17-58)"""
     v = cfg["vision_cfg"]
-    g = v["image_size"] // v["patch_size"]
-    return (g * g if not patch_dropout else patch_keep_count(g * g, patch_dropout)) + 1
+    size = v["image_size"]
+    h, w = (size, size) if isinstance(size, int) else size  # (H, W): a rectangular `force_image_size`
+    g = (h // v["patch_size"]) * (w // v["patch_size"])
+    return (g if not patch_dropout else patch_keep_count(g, patch_dropout)) + 1
 
 
 def count_params(cfg: dict) -> int:
@@ -202,7 +204,8 @@ def forward_gflops_per_pair(cfg: dict, patch_dropout=None) -> float:
     two attention products; the patch embedding; the two projections.  Reproduces the `gflops` column of the reference's
     docs/model_profile.csv for all 28 registered configs it lists to 0.1 % (tests/test_reference_dropin.py).
     ``patch_dropout`` (None / 0: unchanged): the work a training step EXECUTES when the image tower keeps only ``vision_tokens(cfg, patch_dropout)``
-    tokens, the patch embedding of the kept patches included -- the figure to state MFU on when dropout is on."""
+    tokens, the patch embedding of the kept patches included -- the figure to state MFU on when dropout is on.
+    The figure describes the config's own ``image_size``: a call at another size (``dynamic_img_size``) executes its own grid's work."""
     v, t, e = cfg["vision_cfg"], cfg["text_cfg"], cfg["embed_dim"]
 
     def tower(width, layers, tokens, ratio):

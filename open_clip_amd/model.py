@@ -526,6 +526,21 @@ class _VisionEmbedFn(torch.autograd.Function):
         return None, dconv, dcls, dpos, dlnw, dlnb, None, None, None, None, None
 
 
+class _PosResampleFn(torch.autograd.Function):
+    """the learned position table [prefix + Hs*Ws, C] at another grid (ocn_pos_resample_fwd: bicubic, antialiased) and, backward, the transposed map
+    into the learned table's gradient (ocn_pos_resample_bwd: gather form, no atomic -- reproducible whatever ``deterministic`` says)"""
+
+    @staticmethod
+    def forward(ctx, pos, prefix, src_hw, dst_hw):
+        ctx.meta = (prefix, src_hw, dst_hw)
+        return ops.pos_resample(pos.detach().contiguous(), prefix, src_hw, dst_hw, "bicubic", True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        prefix, src_hw, dst_hw = ctx.meta
+        return ops.pos_resample_bwd(dout.contiguous(), prefix, src_hw, dst_hw, "bicubic", True), None, None, None
+
+
 # ------------------------------------------------------------------------------------------------------
 # text embedding (model.py:399-401)
 # ------------------------------------------------------------------------------------------------------
@@ -904,10 +919,17 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
             raise ValueError(f"patch_dropout must satisfy 0 <= prob < 1 (got {patch_dropout!r})")
         # transformer.py:658: an identity placeholder when the option is off
         self.patch_dropout = PatchDropout(patch_dropout) if patch_dropout > 0.0 else nn.Identity()
-        self.image_size = (image_size, image_size)
+        # an int, or (H, W): `force_image_size` may be rectangular (factory.py:462-464 passes it on as it is)
+        image_size = (image_size, image_size) if isinstance(image_size, int) else (int(image_size[0]), int(image_size[1]))
+        if min(image_size) < patch_size:
+            raise ValueError(f"image_size {image_size} holds no patch of {patch_size} x {patch_size}")
+        self.image_size = image_size
         self.patch_size = (patch_size, patch_size)
-        self.grid_size = (image_size // patch_size, image_size // patch_size)
+        self.grid_size = (image_size[0] // patch_size, image_size[1] // patch_size)
         self.pooled_last_block = True  # the last block only on the class-token rows behind the attention (see _PooledBlockFn)
+        # True: a call may bring images of another size (multiples of the patch size, grid sides 1..64); the learned table is resampled to the call's
+        # grid on the device inside the step and its gradient flows back into the learned table (_PosResampleFn).  A plain attribute like the others
+        self.dynamic_img_size = False
         self.output_dim = output_dim
         self.width = width
         scale = width ** -0.5
@@ -922,7 +944,7 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
         self.image_mean = (0.48145466, 0.4578275, 0.40821073)  # OPENAI_DATASET_MEAN / _STD (constants.py:1-2); used by the
         self.image_std = (0.26862954, 0.26130258, 0.27577711)  # uint8 input path only
         # what set_model_preprocess_cfg (model.py:874-878) leaves on the tower: transform.py:18-25 PreprocessCfg as a dict
-        self.preprocess_cfg = {"size": (image_size, image_size), "mode": "RGB", "mean": self.image_mean, "std": self.image_std,
+        self.preprocess_cfg = {"size": image_size, "mode": "RGB", "mean": self.image_mean, "std": self.image_std,
                                "interpolation": "bicubic", "resize_mode": "shortest", "fill_color": 0}
 
     def set_grad_checkpointing(self, enable=True, impl="inline", keep_last=0):
@@ -946,7 +968,8 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
         _lock_layer_groups(self.layer_groups(), unlocked_groups)
 
     def live_tokens(self) -> int:
-        """tokens per image the tower executes as the module stands now: K + 1 in training mode with patch dropout on, else every patch + 1"""
+        """tokens per image the tower executes as the module stands now: K + 1 in training mode with patch dropout on, else every patch + 1 -- at the
+        CONFIGURED image size: a call at another size (``dynamic_img_size``) runs its own grid and is not known here"""
         G = self.grid_size[0] * self.grid_size[1]
         pd = self.patch_dropout
         return (pd.num_keep(G) if self.training and isinstance(pd, PatchDropout) else G) + 1
@@ -968,9 +991,17 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
             norm = (self.image_mean, self.image_std, hwc)
         else:
             hw = tuple(image.shape[2:])
+        pos, grid = self.positional_embedding, tuple(self.grid_size)
         if hw != tuple(self.image_size):
-            raise RuntimeError(f"image size {hw} != {self.image_size}")
-        G = self.grid_size[0] * self.grid_size[1]
+            if not self.dynamic_img_size:
+                raise RuntimeError(f"image size {hw} != {self.image_size}")
+            P = self.patch_size[0]
+            grid = (hw[0] // P, hw[1] // P)
+            if hw[0] % P or hw[1] % P or not (1 <= grid[0] <= 64 and 1 <= grid[1] <= 64):
+                raise RuntimeError(f"dynamic_img_size: image size {hw} must be multiples of the patch size {P} with 1 .. 64 patches per side")
+            # the learned table at the call's grid (bicubic, antialiased: resize_pos_embed's default); a call at the configured size never comes here
+            pos = _PosResampleFn.apply(pos, 1, tuple(self.grid_size), grid)
+        G = grid[0] * grid[1]
         pd, inv = self.patch_dropout, None
         if keep is not None:
             if not (torch.is_tensor(keep) and keep.dtype == torch.int32 and keep.dim() == 2 and keep.shape[0] == B and 1 <= keep.shape[1] <= G):
@@ -983,8 +1014,7 @@ class VisionTransformer(nn.Module):  # transformer.py:592-928 (default path: lea
         T = (G if keep is None else keep.shape[1]) + 1
         drop = () if keep is None else (keep, inv)  # without a plan the call is the one it always was
         lnw, lnb = (self.ln_pre.weight, self.ln_pre.bias) if isinstance(self.ln_pre, LayerNorm) else (None, None)
-        x = _VisionEmbedFn.apply(image, self.conv1.weight, self.class_embedding, self.positional_embedding,
-                                 lnw, lnb, ex, self.patch_size[0], norm, *drop)
+        x = _VisionEmbedFn.apply(image, self.conv1.weight, self.class_embedding, pos, lnw, lnb, ex, self.patch_size[0], norm, *drop)
         if self.pool_type == "avg":  # the mean over the T - 1 patch tokens the tower ran (the kept ones under patch dropout / a caller's keep)
             return _tower_features(self.transformer, x, ex, B, T, False, None, None, None, False, self.ln_post, self.proj, normalize)
         seq = torch.arange(B, device=x.device, dtype=torch.int32)
@@ -1051,7 +1081,7 @@ class NativeCLIP(nn.Module):
 
     def __init__(self, embed_dim, vision_cfg, text_cfg, init_logit_scale=math.log(1 / 0.07), init_logit_bias=None,
                  output_dict=False, *, pack_text=True, tower_streams=True, pooled_last_block=True, attn_buckets=True, pair_wgrad=True,
-                 deterministic=False, quick_gelu=False, image_stream="fp32", **model_kwargs):
+                 deterministic=False, quick_gelu=False, image_stream="fp32", dynamic_img_size=False, **model_kwargs):
         """Reference arguments first (model.py:318-365).  Keyword-only switches of the native execution (every one also a plain attribute
         that may be flipped later; none changes a result beyond fp32 summation order):
         ``pack_text`` -- the text tower holds only the tokens up to the pooled EOT (_TextPack); ``tower_streams`` -- image tower on a
@@ -1065,7 +1095,11 @@ class NativeCLIP(nn.Module):
         (tests/test_model_gpu.py::test_deterministic_step_is_bit_reproducible).
         ``image_stream`` DOES change results, inside the stated tolerances: the dtype of the IMAGE tower's residual stream -- "fp32" (default; stricter than
         the reference), "bf16" (stream and its gradient in bf16 = what the reference's autocast produces there, transformer.py:794 + layers.py:23-26;
-        half the residual-stream bytes of 24 residual epilogues and 49 LayerNorm passes) or "bf16-fp32grad" (bf16 stream, fp32 residual-gradient path)."""
+        half the residual-stream bytes of 24 residual epilogues and 49 LayerNorm passes) or "bf16-fp32grad" (bf16 stream, fp32 residual-gradient path).
+        ``dynamic_img_size`` (``model.visual.dynamic_img_size``, off by default) ADDS calls: the image tower then takes images of any size that is a
+        multiple of the patch size (1 .. 64 patches per side) and resamples its learned position table to the call's grid inside the step (bicubic,
+        antialiased; the gradient flows back into the learned table); a call at the configured size is the call it always was.  The text tower has no
+        per-call form: its length changes at load time only (``create_model(force_context_length=)``)."""
         super().__init__()
         if image_stream not in ("fp32", "bf16", "bf16-fp32grad"):
             raise ValueError(f"image_stream must be 'fp32', 'bf16' or 'bf16-fp32grad' (got {image_stream!r})")
@@ -1083,6 +1117,7 @@ class NativeCLIP(nn.Module):
         self.visual = VisionTransformer(v["image_size"], v["patch_size"], v["width"], v["layers"], v["width"] // head_width,
                                         v.get("mlp_ratio", 4.0), embed_dim, self.quick_gelu, v.get("patch_dropout", 0.0),
                                         bool(v.get("no_ln_pre")), v.get("pool_type") or "tok", bool(v.get("final_ln_after_pool")))
+        self.visual.dynamic_img_size = bool(dynamic_img_size)
         tw = t["width"]
         self.transformer = Transformer(tw, t["layers"], t["heads"], t.get("mlp_ratio", 4.0), self.quick_gelu)
         self.context_length = t["context_length"]
@@ -1189,7 +1224,8 @@ class NativeCLIP(nn.Module):
         3 * mlp_width, + the attention row statistics.  A recomputed block keeps its 4C input only.
         ``text_rows``: rows of the packed text batch (default: every one of ``context_length`` positions).  The image rows are the LIVE ones: in
         training mode with patch dropout on, the class token and the ``num_keep(G)`` kept patches of the random plan (a ``keep`` passed to a
-        single call, whose K' may differ, is not known here and not counted)."""
+        single call, whose K' may differ, is not known here and not counted).  The image rows are those of the CONFIGURED image size
+        (``visual.live_tokens()``): a call at another size under ``dynamic_img_size`` saves in proportion to its own grid."""
         v, t = self.visual, self.transformer
         rows_v = batch_size * v.live_tokens()
         rows_t = batch_size * self.context_length if text_rows is None else int(text_rows)
@@ -1320,12 +1356,84 @@ def convert_to_custom_text_state_dict(state_dict: dict) -> dict:
     return {("text." + k if any(k.startswith(p) for p in _TEXT_KEYS) else k): v for k, v in state_dict.items()}
 
 
+def _resample_entry(state_dict, key, prefix, src_hw, dst_hw, interpolation, antialias, device):
+    """state_dict[key] at another grid through ``ops.pos_resample``: fp32 arithmetic on ``device``, the entry's dtype and device kept"""
+    old = state_dict[key]
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    new = ops.pos_resample(old.detach().to(device=dev, dtype=F32).contiguous(), prefix, src_hw, dst_hw, interpolation, antialias)
+    state_dict[key] = new.to(device=old.device, dtype=old.dtype)
+
+
+def _model_device(model, device):
+    if device is not None:
+        return device
+    p = next(iter(model.parameters()), None) if hasattr(model, "parameters") else None
+    return p.device if p is not None and p.is_cuda else None  # None: the current device
+
+
+def _check_interpolation(name, interpolation):
+    if interpolation not in ops.POS_RESAMPLE_MODES:
+        raise NotImplementedError(f"{name}: interpolation {interpolation!r} is not implemented (one of {sorted(ops.POS_RESAMPLE_MODES)})")
+
+
+def resize_pos_embed(state_dict, model, interpolation: str = "bicubic", antialias: bool = True, *, device=None, old_grid_size=None):
+    """The reference's ``resize_pos_embed`` (model.py:790-821): ``state_dict["visual.positional_embedding"]`` resampled, in place in the dict, to
+    ``model.visual.grid_size`` (one class-token row in front, copied) by ``ocn_pos_resample_fwd`` -- fp32 on the model's device (or ``device``, or the
+    current one); the entry keeps its dtype and device.  Returns silently, without touching the library, when the entry is missing or already fits.
+    ``old_grid_size = (h, w)`` names the grid of a table that is not square; without it such a table raises ``ValueError`` (the reference takes
+    ``int(sqrt())`` silently).  A changed width raises."""
+    _check_interpolation("resize_pos_embed", interpolation)
+    old = state_dict.get("visual.positional_embedding", None)
+    if old is None or not hasattr(model.visual, "grid_size"):
+        return
+    grid = tuple(int(g) for g in model.visual.grid_size)
+    extra = 1
+    if grid[0] * grid[1] + extra == old.shape[0]:
+        return
+    width = model.visual.positional_embedding.shape[1]
+    if old.dim() != 2 or old.shape[1] != width:
+        raise ValueError(f"resize_pos_embed: the width of visual.positional_embedding changed ({tuple(old.shape)} against the model's width {width})")
+    n = old.shape[0] - extra
+    if old_grid_size is not None:
+        old_grid = (int(old_grid_size[0]), int(old_grid_size[1]))
+        if old_grid[0] * old_grid[1] != n:
+            raise ValueError(f"resize_pos_embed: old_grid_size {old_grid} does not hold the table's {n} grid rows")
+    else:
+        side = math.isqrt(n)
+        if side * side != n:
+            raise ValueError(f"resize_pos_embed: the table's {n} grid rows are no perfect square; name its grid with old_grid_size=(h, w)")
+        old_grid = (side, side)
+    _resample_entry(state_dict, "visual.positional_embedding", extra, old_grid, grid, interpolation, antialias, _model_device(model, device))
+
+
+def resize_text_pos_embed(state_dict, model, interpolation: str = "linear", antialias: bool = False, *, device=None):
+    """The reference's ``resize_text_pos_embed`` (model.py:824-854): ``positional_embedding`` (or ``text.positional_embedding``) resampled along the
+    positions, in place in the dict, to the model's context length; same device, dtype and early-return rules as ``resize_pos_embed``."""
+    _check_interpolation("resize_text_pos_embed", interpolation)
+    key = "positional_embedding" if "positional_embedding" in state_dict else "text.positional_embedding"
+    old = state_dict.get(key, None)
+    if old is None:
+        return
+    model_pos = getattr(model, "positional_embedding", None)
+    if model_pos is None:
+        model_pos = model.text.positional_embedding
+    num_pos, width = model_pos.shape
+    if old.dim() != 2 or old.shape[1] != width:
+        raise ValueError(f"resize_text_pos_embed: text pos_embed width changed ({tuple(old.shape)} against the model's width {width})")
+    if old.shape[0] == num_pos:
+        return
+    _resample_entry(state_dict, key, 0, (1, old.shape[0]), (1, num_pos), interpolation, antialias, _model_device(model, device))
+
+
 def create_model(model_name: str, pretrained: Optional[str] = None, precision: str = "amp_bf16", device="cuda",
                  output_dict: Optional[bool] = None, init_logit_scale=None, init_logit_bias=None, force_quick_gelu: bool = False,
-                 force_patch_dropout: Optional[float] = None, **model_kwargs):
+                 force_patch_dropout: Optional[float] = None, force_image_size=None, force_context_length: Optional[int] = None, **model_kwargs):
     """Counterpart of ``open_clip.factory.create_model`` (factory.py:264-287) for the native path.
     ``pretrained`` may be a local ``.pt`` state-dict path (no hub access); ``precision`` must be an
-    amp_bf16-equivalent mode (the kernels implement exactly that policy)."""
+    amp_bf16-equivalent mode (the kernels implement exactly that policy).
+    ``force_image_size`` (an int or (H, W)) / ``force_context_length`` override the config's ``image_size`` / ``context_length`` (factory.py:462-467:
+    ``--force-image-size`` / ``--force-context-length``); a ``pretrained`` checkpoint of another size then has its position tables resampled on the
+    device (``resize_pos_embed`` / ``resize_text_pos_embed``, as load_checkpoint does at factory.py:233-234) in front of the strict load."""
     if precision not in ("amp_bf16", "amp_bfloat16"):
         # the kernels implement exactly one policy: fp32 master weights, bf16 GEMM / attention operands, fp32 accumulation and
         # statistics (= --precision amp_bf16, precision.py:6-17).  fp32 / pure-bf16 / fp16 callers would silently get other numerics.
@@ -1351,6 +1459,11 @@ def create_model(model_name: str, pretrained: Optional[str] = None, precision: s
     kw = {k: v for k, v in kw.items() if v is not None}
     if force_patch_dropout is not None:  # factory.py:460-461: override the config's value (--force-patch-dropout)
         cfg["vision_cfg"] = dict(cfg["vision_cfg"], patch_dropout=force_patch_dropout)
+    if force_image_size is not None:  # factory.py:462-463 (main.py:276: a one-element --force-image-size list arrives as an int, two as (H, W))
+        size = force_image_size if isinstance(force_image_size, int) else tuple(int(s) for s in force_image_size)
+        cfg["vision_cfg"] = dict(cfg["vision_cfg"], image_size=size[0] if not isinstance(size, int) and len(size) == 1 else size)
+    if force_context_length is not None:  # factory.py:466-467
+        cfg["text_cfg"] = dict(cfg["text_cfg"], context_length=int(force_context_length))
     if force_quick_gelu:  # factory.py:521-523: override for checkpoints trained with QuickGELU
         extra_model_kwargs["quick_gelu"] = True
     out_dict = output_dict if output_dict is not None else cfg_output_dict
@@ -1359,5 +1472,8 @@ def create_model(model_name: str, pretrained: Optional[str] = None, precision: s
         sd = torch.load(pretrained, map_location="cpu", weights_only=True)
         sd = sd.get("state_dict", sd)
         sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
-        model.load_state_dict(convert_from_custom_text_state_dict(sd), strict=True)
+        sd = convert_from_custom_text_state_dict(sd)
+        resize_pos_embed(sd, model, device=device)  # factory.py:233-234; both return at once when the tables fit
+        resize_text_pos_embed(sd, model, device=device)
+        model.load_state_dict(sd, strict=True)
     return model.to(device)

@@ -434,6 +434,33 @@ def resample_u8(arena, offsets, plan, size, fill=0, out=None):
     return out
 
 
+POS_RESAMPLE_MODES = {"linear": 0, "bilinear": 0, "bicubic": 1}
+
+
+def _pos_resample(name, t, rows_in, rows_out, prefix, src_hw, dst_hw, mode, antialias):
+    if mode not in POS_RESAMPLE_MODES:
+        raise NotImplementedError(f"{name}: mode {mode!r} is not implemented (one of {sorted(POS_RESAMPLE_MODES)})")
+    if t.dim() != 2 or t.shape[0] != rows_in:
+        raise RuntimeError(f"{name}: the table {tuple(t.shape)} is not [prefix + H*W = {rows_in}, C]")
+    out = empty((rows_out, t.shape[1]), F32, t)
+    _lib.call("ocn_" + name, _chk(t, F32, "table"), _chk(out, F32, "out"), int(prefix), int(src_hw[0]), int(src_hw[1]), int(dst_hw[0]), int(dst_hw[1]),
+              t.shape[1], POS_RESAMPLE_MODES[mode], int(bool(antialias)), _stream())
+    return out
+
+
+def pos_resample(table, prefix, src_hw, dst_hw, mode="bicubic", antialias=True):
+    """a position table at another grid (ocn_pos_resample_fwd; defined in include/openclip_hip.h): ``table`` fp32 [prefix + Hs*Ws, C] ->
+    fp32 [prefix + Ho*Wo, C]; the ``prefix`` rows are copied, the grid rows are ``F.interpolate(size=dst_hw, mode, antialias, align_corners=False)`` per
+    channel.  ``mode``: "bicubic", "bilinear" or "linear"; the 1-D text table is ``src_hw = (1, L)``, ``dst_hw = (1, L')``."""
+    return _pos_resample("pos_resample_fwd", table, prefix + src_hw[0] * src_hw[1], prefix + dst_hw[0] * dst_hw[1], prefix, src_hw, dst_hw, mode, antialias)
+
+
+def pos_resample_bwd(dout, prefix, src_hw, dst_hw, mode="bicubic", antialias=True):
+    """the transposed map (ocn_pos_resample_bwd): ``dout`` fp32 [prefix + Ho*Wo, C], the gradient of ``pos_resample``'s result -> the gradient
+    fp32 [prefix + Hs*Ws, C] of its ``table``; gather form, the same bits every run"""
+    return _pos_resample("pos_resample_bwd", dout, prefix + dst_hw[0] * dst_hw[1], prefix + src_hw[0] * src_hw[1], prefix, src_hw, dst_hw, mode, antialias)
+
+
 def color_jitter_u8(img, factors, plan, out=None):
     """colour jitter + grayscale on the device (ocn_color_jitter_u8; the arithmetic is defined in include/openclip_hip.h): ``img`` uint8 [B, H, W, 3],
     ``factors`` float32 [B, 4] = (brightness, contrast, saturation, hue) and ``plan`` int32 [B] (four 3-bit step codes from the low bits up, bit 12 =

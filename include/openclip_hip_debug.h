@@ -14,7 +14,11 @@ extern "C" {
 #endif
 
 /* kernel choice of ocn_gemm_nt / ocn_gemm_tn_accum (process-global):
- *   bits 0..3  NT kernel: 0 auto, 4 the general 256x256 ring kernel, 5 the persistent 256x256 kernel (falls back to 4)
+ *   bits 0..3  NT kernel: 0 auto, 4 the general 256x256 ring kernel, 5 the persistent 256x256 kernel (falls back to 4),
+ *              6 / 7 the persistent kernel (as 5) whose plain bf16-output launches (OCN_EPI_BF16) run the v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16
+ *              main loop, static and rescue forms alike; 0 and 5 run the form that ships as default (profiles/nt5_mfma_shape.json); both are in
+ *              the product library so that the choice can be re-measured in one process (tools/ab_nt_mfma_shape.py).  Every other epilogue has
+ *              the 32x32x16 loop only
  *   bits 4..7  TN kernel: 0 auto, 1 the general 128x128 kernel, 3 the hand-scheduled 256x256 kernel (falls back to 1),
  *              6 / 7 the hand-scheduled kernel with its v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16 main loop (fall back to 1 exactly as 3
  *              does; single, paired and rescue launches alike).  0 and 3 run the form that ships as default (16x16x32: profiles/tn5_mfma_shape.json);

@@ -421,11 +421,15 @@ constexpr int TN5_DEFAULT_MF16 = 1;
 inline bool tn_hand_forced() { return g_tn_variant == 3 || g_tn_variant == 6 || g_tn_variant == 7; }
 inline int tn_mf16() { return g_tn_variant == 7 ? 1 : (g_tn_variant == 6 ? 0 : TN5_DEFAULT_MF16); }
 int g_nt_ablate = 0;
-int g_nt_variant = 0;  // 0 = auto, 4 = general 256x256 ring kernel (any M, N; K % 32), 5 = persistent 256x256 (gemm_nt5.hip; K % 128)
+int g_nt_variant = 0;  // 0 = auto, 4 = general 256x256 ring kernel (any M, N; K % 32), 5 = persistent 256x256 (gemm_nt5.hip; K % 128), 6 / 7 = 5 with the 32x32x16 / 16x16x32 main loop for its bf16-out launches
+// MFMA shape of the persistent kernel's OCN_EPI_BF16 main loop under variants 0 and 5: the form with the lower summed wall time over the step's
+// bf16-out launches (profiles/nt5_mfma_shape.json); 6 and 7 keep both selectable in one process
+constexpr int NT5_DEFAULT_MF16 = 1;
 
 template <int EPI>
 int launch_nt(const GemmNtArgs& a, hipStream_t st) {
     int v = g_nt_variant;
+    if (v == 6 || v == 7) v = 5;
     if (v == 0) v = (a.M >= 1024 && a.N >= 192) ? 5 : 4;
     if (v == 5) {  // persistent 256x256 kernel (gemm_nt5.hip); falls through to the general kernel when the shape does not fit it
         GemmNtArgs a5 = a;
@@ -448,6 +452,8 @@ int launch_nt(const GemmNtArgs& a, hipStream_t st) {
 }
 
 }  // namespace
+
+int ocn_nt5_mf16() { return g_nt_variant == 7 ? 1 : (g_nt_variant == 6 ? 0 : NT5_DEFAULT_MF16); }
 
 extern "C" int ocn_gemm_nt(int epilogue, const void* A, int lda, const void* B, int ldb, void* out, int ldc, int M, int N,
                            int K, const float* bias, const void* resid, void* aux, float alpha, ocn_stream_t stream) {

@@ -44,6 +44,9 @@ OCN_DEV int swz_nt(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 
 // persistent 256x256 NT kernel (gemm_nt5.hip); returns 1 if the shape is not supported by it (caller falls back)
 int ocn_launch_nt5(int epilogue, const GemmNtArgs& a, hipStream_t st);
+// main loop of the persistent kernel's OCN_EPI_BF16 launches (gemm.hip: ocn_set_gemm_variant's NT values 6 / 7, else the compile-time default):
+// 0 = v_mfma_f32_32x32x16_bf16, 1 = v_mfma_f32_16x16x32_bf16
+int ocn_nt5_mf16();
 
 struct GemmTnArgs {
     const bf16* A;

@@ -412,6 +412,55 @@ OCN_DEV void epilogue5(const GemmNtArgs& a, f32x16 (&acc)[2][2][2], int m0, int 
     }
 }
 
+// Plain bf16 epilogue (OCN_EPI_BF16) of the 16x16x32 main loop (MF16): the accumulators are 16 x 16 C^T blocks -- lane l, register r of block
+// (mb, nb) of half ha is C row ha*64 + mb*16 + (l & 15), column nb*16 + 4*(l >> 4) + r.  Conversion, alpha and bias in that layout, then the same
+// transpose through the wave's 4 KiB staging buffer (32 rows x 128 bytes per 32 x 64 sub-block, chunk ^ (row & 7) swizzle), the same read-back and
+// the same row-wise 16-byte buffer stores as epilogue5's OCN_EPI_BF16 path: only the staging write address and the bias column differ.
+template <int AUX>
+OCN_DEV void epilogue5_bf16_m16(const GemmNtArgs& a, f32x4 (&acc)[2][4][4], int m0, int n0, int wm, int wn, int lane, unsigned stg, int ha_n, int row_shift) {
+    int lane_o = lane;
+    asm volatile("" : "+v"(lane_o));  // see epilogue5: keeps the address arithmetic out of the tile loop's live set
+    const int l15 = lane_o & 15, l4 = lane_o >> 4;
+    const int gn_w = n0 + wn * 64;
+    const int rd_row = lane_o >> 3, rd_chunk = lane_o & 7;
+    const unsigned rd_addr = stg + rd_row * 128 + ((rd_chunk ^ rd_row) << 4);  // + it * 1024 for rows it*8 + rd_row
+    const int m_st = ABL(a, 32) ? 0 : a.M;
+    const __amdgpu_buffer_rsrc_t r_out = tile_rsrc(a.out, m0, m_st, a.ldc, 2);
+    const __amdgpu_buffer_rsrc_t r_bias = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, a.bias ? a.N * 4 : 0, 0x00020000);
+    f32x4 bv[4];  // fetched once, before any store of this tile is issued; added before rounding
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) bv[nb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_bias, (gn_w + nb * 16 + 4 * l4) * 4, 0, 0));
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every DMA issued so far has landed (see epilogue5)
+    const int row_w = wm * 128 + row_shift;  // this wave's first row inside the tile
+    const int gn = gn_w + rd_chunk * 8;
+    const unsigned col_off = gn < a.N ? (unsigned)gn * 2u : OOB;
+#pragma unroll
+    for (int ha = 0; ha < 2; ++ha) {
+        if (ha >= ha_n) break;  // uniform
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int row = i * 16 + l15;  // row of the 32-row sub-block
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb) {
+                    const f32x4 v = acc[ha][s * 2 + i][nb] * a.alpha + bv[nb];
+                    const bf16x4 pk = {f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+                    lds_w64(stg + row * 128 + (((nb * 2 + (l4 >> 1)) ^ (row & 7)) << 4) + (l4 & 1) * 8, pk);  // byte nb*32 + 8*l4 of the row
+                }
+            }
+            bf16x8 d[4];
+            lds_r128x4(rd_addr, rd_addr + 1024, rd_addr + 2048, rd_addr + 3072, d[0], d[1], d[2], d[3]);
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int row = row_w + ha * 64 + s * 32 + it * 8 + rd_row;
+                const unsigned off = (unsigned)(row * a.ldc) * 2u + col_off;
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, d[it]), r_out, off, 0, AUX & 2);
+            }
+        }
+    }
+}
+
 // DBG = developer build of the same kernel that logs a per-tile timeline into a.aux (tools/gemm_trace.py; plain bf16
 // epilogue only); the production instantiation folds it away.
 // AUX = cache policy of the epilogue: bit 1 (2) = non-temporal stores, bit 3 (8) = non-temporal loads of the residual / saved operand
@@ -421,8 +470,14 @@ OCN_DEV void epilogue5(const GemmNtArgs& a, f32x16 (&acc)[2][2][2], int m0, int 
 // finisher can claim from it afterwards), a finisher claims entry k of share w with one atomicAdd(+1) (valid while k < the share's length).  No atomic
 // sits inside the tile loop: the DMA pipeline's counted vmcnt waits retire in issue order and would stall behind one.
 constexpr int RESCUE_BIG = 1 << 20;
-template <int EPI, bool DBG, int AUX = 0, bool RESCUE = false>
+// MF16 (OCN_EPI_BF16 only; ocn_nt5_mf16): the main loop on v_mfma_f32_16x16x32_bf16 -- a K-tile is two 32-wide k-steps, a phase 4 m-blocks x 4 n-blocks x
+// 2 k-steps = 32 MFMAs of 16 x 16 (the same 512 MFMA cycles as 16 of 32 x 32 x 16) in four groups of eight, (k-step, m-block pair) = (0, 0) (0, 1) (1, 0)
+// (1, 1).  The LDS image, the DMA ring, the waits and the barriers are the 32x32x16 loop's; only the fragment reads, the MFMA groups and the
+// accumulators (16 x 16 C^T blocks, epilogue5_bf16_m16) differ.  For a 16-row block lane l supplies row l & 15 and k = 8 (l >> 4) .. + 7 of a k-step:
+// one ds_read_b128 at chunk (kstep * 4 + (l >> 4)) ^ swz of the 128-byte row.
+template <int EPI, bool DBG, int AUX = 0, bool RESCUE = false, bool MF16 = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
+    static_assert(!MF16 || EPI == OCN_EPI_BF16, "the 16x16x32 main loop has the plain bf16 epilogue only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -458,6 +513,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
             const unsigned o = (unsigned)((q << 4) ^ (ks << 5));
             va[ks] = lds_base + (unsigned)((wm * 64 + lr) * 128) + o;
             vb[ks] = lds_base + 65536u + (unsigned)((wn * 32 + lr) * 128) + o;
+        }
+    }
+    // MF16: unit row (wave strip + lane&15; + 16 rows per block in the immediate), chunk ((kstep*4 + (lane>>4)) ^ swz) = (q<<4) ^ (kstep<<6)
+    unsigned va16[2], vb16[2];
+    {
+        const int l15 = lane & 15;
+        const int q = (lane >> 4) ^ swz_nt(l15);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const unsigned o = (unsigned)((q << 4) ^ (ks << 6));
+            va16[ks] = lds_base + (unsigned)((wm * 64 + l15) * 128) + o;
+            vb16[ks] = lds_base + 65536u + (unsigned)((wn * 32 + l15) * 128) + o;
         }
     }
 
@@ -593,6 +660,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
     f32x16 acc[2][2][2];  // [A half][32-row sub-block][B half], each a 32x32 C^T tile
     bf16x8 fa[2][2];      // A fragments: [buffer][sub-block]
     bf16x8 fb[2][4];      // B fragments of the whole K-tile: [B half][k-substep]
+    f32x4 acc16[2][4][4];  // MF16: [A half][16-row m-block][16-column n-block], each a 16x16 C^T tile
+    bf16x8 fa16[2][2];     // MF16 A fragments: [buffer][m-block of the pair]
+    bf16x8 fb16[4][2];     // MF16 B fragments of the whole K-tile: [n-block][k-step]
     const unsigned stg = lds_base + RING_BYTES + wave * STG_BYTES;
     long long* dbg = nullptr;
 #ifdef OCN_DEV_BUILD
@@ -726,12 +796,93 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
         PRIO_OFF() SB(); LGKM0(); SB();                                                                      \
     }
 
+    // ---- MF16 forms of the same macros (see the kernel's head) ----
+#define RD_A16(FA, KS, MBP, HA, P) DSR(FA[0], va16[KS], A_SLOT(HA, P) + (MBP)*4096); DSR(FA[1], va16[KS], A_SLOT(HA, P) + (MBP)*4096 + 2048);
+#define RD_B16(NB, KS, P) DSR(fb16[NB][KS], vb16[KS], B_RD((NB) >> 1, P) + ((NB) & 1) * 2048);
+#define M16(HA, MB, NB, AF, KS) acc16[HA][MB][NB] = mfma16(fb16[NB][KS], AF, acc16[HA][MB][NB]);
+#define MM16(HA, FA, MBP, KS)                                                                       \
+    M16(HA, (MBP)*2, 0, FA[0], KS) M16(HA, (MBP)*2, 1, FA[0], KS) M16(HA, (MBP)*2, 2, FA[0], KS) M16(HA, (MBP)*2, 3, FA[0], KS) \
+    M16(HA, (MBP)*2 + 1, 0, FA[1], KS) M16(HA, (MBP)*2 + 1, 1, FA[1], KS) M16(HA, (MBP)*2 + 1, 2, FA[1], KS) M16(HA, (MBP)*2 + 1, 3, FA[1], KS)
+    // (only OCN_EPI_BF16 runs this loop: no epilogue-operand prefetch, PFN = 0, so the counted waits are the plain 6 / 2)
+#define KTILE16(P, SKIP, LAST)                                                                    \
+    {                                                                                             \
+        /* ---- even phase: A0 x (B0, B1) ---- */                                                 \
+        if (!(SKIP)) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                             \
+        __builtin_amdgcn_s_barrier();                                                             \
+        SB();                                                                                     \
+        RD_A16(fa16[1], 0, 1, 0, P) RD_B16(0, 1, P) RD_B16(1, 1, P)                               \
+        SB(); PRIO_ON()                                                                           \
+        M16(0, 0, 0, fa16[0][0], 0) M16(0, 0, 1, fa16[0][0], 0)                                   \
+        DMA_A1(0, (P) ^ 1)                                                                        \
+        M16(0, 0, 2, fa16[0][0], 0) M16(0, 0, 3, fa16[0][0], 0)                                   \
+        M16(0, 1, 0, fa16[0][1], 0) M16(0, 1, 1, fa16[0][1], 0)                                   \
+        DMA_A1(1, (P) ^ 1)                                                                        \
+        M16(0, 1, 2, fa16[0][1], 0) M16(0, 1, 3, fa16[0][1], 0)                                   \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        RD_A16(fa16[0], 1, 0, 0, P) RD_B16(2, 1, P) RD_B16(3, 1, P)                               \
+        SB(); PRIO_ON()                                                                           \
+        MM16(0, fa16[1], 1, 0)                                                                    \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        RD_A16(fa16[1], 1, 1, 0, P)                                                               \
+        SB(); PRIO_ON()                                                                           \
+        MM16(0, fa16[0], 0, 1)                                                                    \
+        adv_a1();                                                                                 \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        RD_A16(fa16[0], 0, 0, 1, P)                                                               \
+        SB(); PRIO_ON()                                                                           \
+        MM16(0, fa16[1], 1, 1)                                                                    \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        /* ---- odd phase: A1 x (B0, B1), B fragments from registers ---- */                      \
+        if (!(SKIP)) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                             \
+        __builtin_amdgcn_s_barrier();                                                             \
+        SB();                                                                                     \
+        RD_A16(fa16[1], 0, 1, 1, P)                                                               \
+        SB(); PRIO_ON()                                                                           \
+        M16(1, 0, 0, fa16[0][0], 0) M16(1, 0, 1, fa16[0][0], 0)                                   \
+        DMA_A0(0, P)                                                                              \
+        M16(1, 0, 2, fa16[0][0], 0) M16(1, 0, 3, fa16[0][0], 0)                                   \
+        DMA_A0(1, P)                                                                              \
+        M16(1, 1, 0, fa16[0][1], 0) M16(1, 1, 1, fa16[0][1], 0)                                   \
+        DMA_B0(0, P)                                                                              \
+        M16(1, 1, 2, fa16[0][1], 0) M16(1, 1, 3, fa16[0][1], 0)                                   \
+        DMA_B0(1, P)                                                                              \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        RD_A16(fa16[0], 1, 0, 1, P)                                                               \
+        SB(); PRIO_ON()                                                                           \
+        M16(1, 2, 0, fa16[1][0], 0) M16(1, 2, 1, fa16[1][0], 0)                                   \
+        DMA_B1(0, P)                                                                              \
+        M16(1, 2, 2, fa16[1][0], 0) M16(1, 2, 3, fa16[1][0], 0)                                   \
+        DMA_B1(1, P)                                                                              \
+        M16(1, 3, 0, fa16[1][1], 0) M16(1, 3, 1, fa16[1][1], 0)                                   \
+        M16(1, 3, 2, fa16[1][1], 0) M16(1, 3, 3, fa16[1][1], 0)                                   \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        /* from here: first fragments of the next K-tile too (ring parity P^1; published by this phase's barrier) */ \
+        RD_A16(fa16[1], 1, 1, 1, P)                                                               \
+        if (!(LAST)) { RD_B16(0, 0, (P) ^ 1) RD_B16(1, 0, (P) ^ 1) }                              \
+        SB(); PRIO_ON()                                                                           \
+        MM16(1, fa16[0], 0, 1)                                                                    \
+        adv_ab();                                                                                 \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+        if (!(LAST)) { RD_A16(fa16[0], 0, 0, 0, (P) ^ 1) RD_B16(2, 0, (P) ^ 1) RD_B16(3, 0, (P) ^ 1) } \
+        SB(); PRIO_ON()                                                                           \
+        MM16(1, fa16[1], 1, 1)                                                                    \
+        PRIO_OFF() SB(); LGKM0(); SB();                                                           \
+    }
+
 #define STAMP(IDX) if (DBG && dbg && i < 8) dbg[i * 8 + (IDX)] = wall_clock64();
 #if (OCN_PRIO_MODE & 2)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
     for (int i = 0; i < my_tiles; ++i) {
         STAMP(0)
+        if constexpr (MF16) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 4; ++y)
+#pragma unroll
+                    for (int z = 0; z < 4; ++z) acc16[x][y][z] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        } else {
 #pragma unroll
         for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -740,13 +891,27 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
                 for (int z = 0; z < 2; ++z)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[x][y][z][r] = 0.f;
+        }
         // first fragments of the tile (its K-tile 0 was published by a barrier before the previous epilogue / prologue)
         SB();
-        RD_A(fa[0], 0, 0, 0) RD_B(0, 0)
+        if constexpr (MF16) { RD_A16(fa16[0], 0, 0, 0, 0) RD_B16(0, 0, 0) RD_B16(1, 0, 0) RD_B16(2, 0, 0) RD_B16(3, 0, 0) }
+        else { RD_A(fa[0], 0, 0, 0) RD_B(0, 0) }
         LGKM0();
         SB();
         int pm0, pn0, pks;
         tile_origin(i, pm0, pn0, pks);
+        if constexpr (MF16) {
+            for (int kt = 0; kt + 2 < nk; kt += 2) {
+                const bool skip = (kt == 0);
+                KTILE16(0, skip, false)
+                KTILE16(1, false, false)
+            }
+            {
+                const bool skip = (nk == 2);
+                KTILE16(0, skip, false)
+                KTILE16(1, false, true)
+            }
+        } else {
         for (int kt = 0; kt + 2 < nk; kt += 2) {
             const bool skip = (kt == 0);
             KTILE(0, skip, false, 0)
@@ -757,8 +922,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
             KTILE(0, skip, false, 1)
             KTILE(1, false, true, 2)
         }
+        }
         STAMP(3)
-        epilogue5<EPI, AUX>(a, acc, pm0, pn0, wm, wn, lane, stg, pf, 2, 0, (DBG && dbg && i < 8) ? dbg + i * 8 : nullptr, pks);
+        if constexpr (MF16) epilogue5_bf16_m16<AUX>(a, acc16, pm0, pn0, wm, wn, lane, stg, 2, 0);
+        else epilogue5<EPI, AUX>(a, acc, pm0, pn0, wm, wn, lane, stg, pf, 2, 0, (DBG && dbg && i < 8) ? dbg + i * 8 : nullptr, pks);
         if (ABL(a, 4)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // developer knob: let the tile's stores drain before the next main loop
         if constexpr (PFN > 0) __builtin_amdgcn_s_barrier();  // publishes the next tile's first K-tile (see KTILE, PFM = 2)
         STAMP(4)
@@ -804,16 +971,24 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
         else { const unsigned so_ = (ka < k_end ? ka : k_last) + hoff; DMA(dA0, voA, so_, SLOT, (N) & 1) }              \
     }
             HDMA_A(A_SLOT(0, 0)) HDMA_B(0) HDMA_A(A_SLOT(0, 1)) HDMA_B(1) HDMA_A(A_SLOT(1, 0)) HDMA_A(A_SLOT(1, 1))
+            if constexpr (MF16) {
+#pragma unroll
+                for (int y = 0; y < 4; ++y)
+#pragma unroll
+                    for (int z = 0; z < 4; ++z) acc16[0][y][z] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            } else {
 #pragma unroll
             for (int y = 0; y < 2; ++y)
 #pragma unroll
                 for (int z = 0; z < 2; ++z)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[0][y][z][r] = 0.f;
+            }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             SB();
-            RD_A(fa[0], 0, 0, 0) RD_B(0, 0)
+            if constexpr (MF16) { RD_A16(fa16[0], 0, 0, 0, 0) RD_B16(0, 0, 0) RD_B16(1, 0, 0) RD_B16(2, 0, 0) RD_B16(3, 0, 0) }
+            else { RD_A(fa[0], 0, 0, 0) RD_B(0, 0) }
             LGKM0();
             SB();
             // K-tile g = 4 n + Q: A unit in ring slot Q (= A_SLOT(Q >> 1, Q & 1)), B units in parity Q & 1
@@ -848,13 +1023,47 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
         kb += 128; ka += 128;                                                                           \
         SB(); LGKM0(); SB();                                                                            \
     }
-            for (int kt = 0; kt < nk; kt += 4) { HKT(0) HKT(1) HKT(2) HKT(3) }
+            // MF16: the same phase in four groups of eight MFMAs; the last group runs behind the barrier from registers while the slot is refilled
+#define HKT16(Q)                                                                                        \
+    {                                                                                                   \
+        RD_A16(fa16[1], 0, 1, (Q) >> 1, (Q) & 1) RD_B16(0, 1, (Q) & 1) RD_B16(1, 1, (Q) & 1)            \
+        SB();                                                                                           \
+        MM16(0, fa16[0], 0, 0)                                                                          \
+        SB(); LGKM0(); SB();                                                                            \
+        RD_A16(fa16[0], 1, 0, (Q) >> 1, (Q) & 1) RD_B16(2, 1, (Q) & 1) RD_B16(3, 1, (Q) & 1)            \
+        SB();                                                                                           \
+        MM16(0, fa16[1], 1, 0)                                                                          \
+        SB(); LGKM0(); SB();                                                                            \
+        RD_A16(fa16[1], 1, 1, (Q) >> 1, (Q) & 1)                                                        \
+        SB();                                                                                           \
+        MM16(0, fa16[0], 0, 1)                                                                          \
+        SB(); LGKM0(); SB();                                                                            \
+        asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                                \
+        __builtin_amdgcn_s_barrier();                                                                   \
+        SB();                                                                                           \
+        RD_A16(fa16[0], 0, 0, (((Q) + 1) & 3) >> 1, ((Q) + 1) & 1)                                      \
+        RD_B16(0, 0, ((Q) + 1) & 1) RD_B16(1, 0, ((Q) + 1) & 1) RD_B16(2, 0, ((Q) + 1) & 1) RD_B16(3, 0, ((Q) + 1) & 1) \
+        SB();                                                                                           \
+        M16(0, 2, 0, fa16[1][0], 1) M16(0, 2, 1, fa16[1][0], 1)                                         \
+        HPIECE(0, (Q) & 1, 0) HPIECE(1, (Q) & 1, 0)                                                     \
+        M16(0, 2, 2, fa16[1][0], 1) M16(0, 2, 3, fa16[1][0], 1)                                         \
+        HPIECE(2, (Q) & 1, 0) HPIECE(3, (Q) & 1, 0)                                                     \
+        M16(0, 3, 0, fa16[1][1], 1) M16(0, 3, 1, fa16[1][1], 1)                                         \
+        HPIECE(4, 0, A_SLOT((Q) >> 1, (Q) & 1)) HPIECE(5, 0, A_SLOT((Q) >> 1, (Q) & 1))                  \
+        M16(0, 3, 2, fa16[1][1], 1) M16(0, 3, 3, fa16[1][1], 1)                                         \
+        kb += 128; ka += 128;                                                                           \
+        SB(); LGKM0(); SB();                                                                            \
+    }
+            if constexpr (MF16) { for (int kt = 0; kt < nk; kt += 4) { HKT16(0) HKT16(1) HKT16(2) HKT16(3) } }
+            else { for (int kt = 0; kt < nk; kt += 4) { HKT(0) HKT(1) HKT(2) HKT(3) } }
 #undef HKT
+#undef HKT16
 #undef HDMA_A
 #undef HDMA_B
 #undef HPIECE
             epi_prefetch<EPI, AUX>(a, m0, n0, wm * 128 + h * 64, wn, lane, pf);
-            epilogue5<EPI, AUX>(a, acc, m0, n0, wm, wn, lane, stg, pf, 1, h * 64);
+            if constexpr (MF16) epilogue5_bf16_m16<AUX>(a, acc16, m0, n0, wm, wn, lane, stg, 1, h * 64);
+            else epilogue5<EPI, AUX>(a, acc, m0, n0, wm, wn, lane, stg, pf, 1, h * 64);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing prefetches must land before the LDS is released
@@ -892,9 +1101,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
     }
   }  // pass
 #undef KTILE
+#undef KTILE16
 #undef MM
+#undef MM16
+#undef M16
 #undef RD_A
 #undef RD_B
+#undef RD_A16
+#undef RD_B16
 #undef DMA
 #undef DMA_NT
 #undef DMA_A1
@@ -944,26 +1158,26 @@ int nt5_stagger(int ntiles, int K, int forced) {
     return tile_us * 100 / 4;
 }
 
-template <int EPI, int AUXV>
+template <int EPI, int AUXV, bool MF16 = false>
 int launch5_aux(GemmNtArgs a, int grid, hipStream_t st) {
     static bool set_ = false;
     if (!set_) {
-        (void)hipFuncSetAttribute((const void*)gemm_nt5_kernel<EPI, false, AUXV>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm_nt5_kernel<EPI, false, AUXV, false, MF16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #ifndef OCN_DEV_BUILD
-        (void)hipFuncSetAttribute((const void*)gemm_nt5_kernel<EPI, false, AUXV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)gemm_nt5_kernel<EPI, false, AUXV, true, MF16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 #endif
         set_ = true;
     }
 #ifndef OCN_DEV_BUILD  // (the developer build's many cache-policy instantiations exist in the static form only)
     a.rescue = grid > 1 ? ocn_rescue_board(st, grid) : nullptr;
     if (a.rescue) {
-        hipLaunchKernelGGL((gemm_nt5_kernel<EPI, false, AUXV, true>), dim3(grid), dim3(512), LDS_BYTES, st, a);
+        hipLaunchKernelGGL((gemm_nt5_kernel<EPI, false, AUXV, true, MF16>), dim3(grid), dim3(512), LDS_BYTES, st, a);
         OCN_CHECK_LAUNCH("ocn_gemm_nt");
         return OCN_OK;
     }
 #endif
     a.rescue = nullptr;
-    hipLaunchKernelGGL((gemm_nt5_kernel<EPI, false, AUXV>), dim3(grid), dim3(512), LDS_BYTES, st, a);
+    hipLaunchKernelGGL((gemm_nt5_kernel<EPI, false, AUXV, false, MF16>), dim3(grid), dim3(512), LDS_BYTES, st, a);
     OCN_CHECK_LAUNCH("ocn_gemm_nt");
     return OCN_OK;
 }
@@ -1033,6 +1247,9 @@ int launch5(GemmNtArgs a, hipStream_t st) {
     }
     // developer knob bits 2 / 8 flip the store / load policy, bit 16 fetches the A operand non-temporally
     const int aux = ((st_nt != ((a.ablate & 2) != 0)) ? 2 : 0) | ((ld_nt != ((a.ablate & 8) != 0)) ? 8 : 0) | ((a.ablate & 16) ? 16 : 0);
+    if constexpr (EPI == OCN_EPI_BF16) {  // the 16x16x32 main loop exists for the two store policies the product uses
+        if (ocn_nt5_mf16() && (aux & ~2) == 0) return aux ? launch5_aux<EPI, 2, true>(a, grid, st) : launch5_aux<EPI, 0, true>(a, grid, st);
+    }
     switch (aux) {
         case 0: return launch5_aux<EPI, 0>(a, grid, st);
         case 2: return launch5_aux<EPI, 2>(a, grid, st);
@@ -1048,7 +1265,11 @@ int launch5(GemmNtArgs a, hipStream_t st) {
     if constexpr (is_gelu) return launch5_aux<EPI, 2>(a, grid, st);
     else if constexpr (EPI == OCN_EPI_BIAS_RESID_F32 || EPI == OCN_EPI_BIAS_RESID_BF16) return launch5_aux<EPI, 8>(a, grid, st);
     else if constexpr (EPI == OCN_EPI_DGELU) return st_nt ? launch5_aux<EPI, 10>(a, grid, st) : launch5_aux<EPI, 8>(a, grid, st);
-    else if constexpr (EPI == OCN_EPI_BF16) return st_nt ? launch5_aux<EPI, 2>(a, grid, st) : launch5_aux<EPI, 0>(a, grid, st);
+    else if constexpr (EPI == OCN_EPI_BF16) {
+        // main loop on 16x16x32 or 32x32x16 MFMAs (ocn_nt5_mf16); the rescue and static forms of a launch share it (launch5_aux)
+        if (ocn_nt5_mf16()) return st_nt ? launch5_aux<EPI, 2, true>(a, grid, st) : launch5_aux<EPI, 0, true>(a, grid, st);
+        return st_nt ? launch5_aux<EPI, 2>(a, grid, st) : launch5_aux<EPI, 0>(a, grid, st);
+    }
     else return launch5_aux<EPI, 0>(a, grid, st);
 #endif
 }

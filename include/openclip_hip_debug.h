@@ -19,10 +19,9 @@ extern "C" {
  *              main loop, static and rescue forms alike; 0 and 5 run the form that ships as default (profiles/nt5_mfma_shape.json); both are in
  *              the product library so that the choice can be re-measured in one process (tools/ab_nt_mfma_shape.py).  Every other epilogue has
  *              the 32x32x16 loop only
- *   bits 4..7  TN kernel: 0 auto, 1 the general 128x128 kernel, 3 the hand-scheduled 256x256 kernel (falls back to 1),
- *              6 / 7 the hand-scheduled kernel with its v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16 main loop (fall back to 1 exactly as 3
- *              does; single, paired and rescue launches alike).  0 and 3 run the form that ships as default (16x16x32: profiles/tn5_mfma_shape.json);
- *              both forms are in the product library so that the choice can be re-measured in one process (tools/ab_tn_mfma_shape.py)
+ *   bits 4..7  TN kernel: 0 auto, 1 the general 128x128 kernel, 3 the hand-scheduled 256x256 kernel (falls back to 1; single, paired and rescue
+ *              launches alike).  Values 6 / 7 selected between two main loops of that kernel until the 32x32x16 one was removed
+ *              (profiles/tn5_mfma_shape.json, profiles/variants_retired.json): they now fail with OCN_ERR_INVALID and change nothing
  *   bits 8..   developer knobs of the persistent NT kernel: (v >> 8) & 1 skip GELU arithmetic (results wrong), & 2 / & 8 flip the
  *              epilogue's store / load cache policy, & 4 drain stores per tile, & 16 non-temporal A-operand loads, & 32 / & 128 drop the
  *              epilogue's stores / operand loads (results wrong), & 64 timeline build, & 0x200000 whole tail tiles instead of half tiles,
@@ -36,14 +35,11 @@ int ocn_set_gemm_variant(int nt_variant);
 /* developer knobs (process-global; experiments and A/B measurements of tools/sweep.py, never needed by a user):
  *   key 1  attention-backward ablation mask (1 skip the input staging, 2 skip the arithmetic, 4 skip the stores: results wrong)
  *   key 3  persistent NT GEMM (developer build): which workgroups share a start-stagger class: 0 consecutive workgroups alternate (shipped), 1 per XCD, 2 per tile row of the band
- *   key 2  attention backward: 4 = two-pass dK / dV build, 5 = one-pass build (default: two-pass up to 4 waves)   key 4  wgrad GEMM: 1 = skip the atomic epilogue,
- *          4 = (developer build) stamp s_memtime / s_memrealtime around the main loop; ocn_debug_nt5_trace then returns those stamps (tools/ab_tn_mfma_shape.py --stamps)
+ *   key 2  attention backward: 4 = two-pass dK / dV build, 5 = one-pass build (default: two-pass up to 4 waves)   key 4  wgrad GEMM: 1 = skip the atomic epilogue
  *   key 5  attention backward: extra KiB of LDS per workgroup (occupancy probe)  key 6  1 = generic instead of causal bwd kernel
  *   key 7  1 = always the streamed (explicit head_dim) attention kernels, 2 = always the head-resident ones (head_dim 64, L <= 320)
- *   key 8  1 = LayerNorm backward, default cache policy
  *   key 9  2 = attention forward, non-temporal policy for its LDS-DMA loads
  *   key 10 workgroups per CU of the persistent NT GEMM's grid (0 = default 1)   key 11 wgrad GEMM: M-splits per CU when few (0/1 = one)
- *   key 12 1 = LayerNorm forward, default cache policy for x (default: non-temporal)
  *   key 13 1 = ocn_gemm_tn_accum2 never pairs (runs its two problems as two launches: A/B of the paired wgrad)
  *   key 14 n = workgroups of the LayerNorm backward's grid (default: one 16-wave workgroup per CU) */
 int ocn_set_tuning(int key, int value);

@@ -18,6 +18,17 @@ void ocn_set_error(const char* fmt, ...) {
 extern "C" const char* ocn_last_error(void) { return g_err; }
 extern "C" int ocn_version(void) { return OCN_ABI_VERSION; }
 
+int ocn_num_cus() {
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n;
+    }
+    return cus;
+}
+
 // developer tuning / ablation knobs (process-global; timing experiments only)
 int g_ocn_tuning[16] = {0};
 extern "C" int ocn_set_tuning(int key, int value) {

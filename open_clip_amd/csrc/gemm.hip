@@ -414,12 +414,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmTnArgs a) {
     }
 }
 
-int g_tn_variant = 0;  // 0 = auto, 1 = general 128x128 kernel, 3 = 256x256 hand-scheduled (gemm_tn5.hip), 6 / 7 = the same with its 32x32x16 / 16x16x32 main loop
-// MFMA shape of the hand-scheduled kernel's main loop under variants 0 and 3: the form with the lower summed wall time over the step's wgrad
-// launches (profiles/tn5_mfma_shape.json); 6 and 7 keep both selectable in one process
-constexpr int TN5_DEFAULT_MF16 = 1;
-inline bool tn_hand_forced() { return g_tn_variant == 3 || g_tn_variant == 6 || g_tn_variant == 7; }
-inline int tn_mf16() { return g_tn_variant == 7 ? 1 : (g_tn_variant == 6 ? 0 : TN5_DEFAULT_MF16); }
+int g_tn_variant = 0;  // 0 = auto, 1 = general 128x128 kernel, 3 = 256x256 hand-scheduled (gemm_tn5.hip)
+inline bool tn_hand_forced() { return g_tn_variant == 3; }
 int g_nt_ablate = 0;
 int g_nt_variant = 0;  // 0 = auto, 4 = general 256x256 ring kernel (any M, N; K % 32), 5 = persistent 256x256 (gemm_nt5.hip; K % 128), 6 / 7 = 5 with the 32x32x16 / 16x16x32 main loop for its bf16-out launches
 // MFMA shape of the persistent kernel's OCN_EPI_BF16 main loop under variants 0 and 5: the form with the lower summed wall time over the step's
@@ -509,21 +505,14 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         *(f32x4*)(out + o) = v * sc;
     }
 }
-int g_splitk_cus = 0;
 }  // namespace
 
 // K-slices a [M, N] = A[M, K] . B[N, K]^T product should be cut into so that its 256 x 256 tiles fill the chip: 1 (= use ocn_gemm_nt) unless the
 // tiles cover at most half of the CUs and every slice keeps K >= 1024 (a multiple of 128)
 extern "C" int ocn_gemm_nt_splitk_plan(int M, int N, int K) {
-    if (g_splitk_cus == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_splitk_cus = n;
-    }
     const int tiles = ocn_cdiv(M, 256) * ocn_cdiv(N, 256);
     int ks = 1;
-    while (tiles * ks * 2 <= g_splitk_cus && K % (128 * ks * 2) == 0 && K / (ks * 2) >= 1024) ks *= 2;
+    while (tiles * ks * 2 <= ocn_num_cus() && K % (128 * ks * 2) == 0 && K / (ks * 2) >= 1024) ks *= 2;
     return (M >= 1024 && N >= 192 && N % 8 == 0) ? ks : 1;
 }
 
@@ -552,8 +541,10 @@ extern "C" int ocn_gemm_nt_splitk(const void* A, int lda, const void* B, int ldb
 }
 
 extern "C" int ocn_set_gemm_variant(int nt_variant) {
+    const int tn = (nt_variant >> 4) & 15;
+    OCN_CHECK_ARG(tn != 6 && tn != 7, "ocn_set_gemm_variant: TN value %d is gone: the hand-scheduled wgrad kernel has the 16x16x32 main loop only (use 3)", tn);
     g_nt_ablate = nt_variant >> 8;   // developer ablation mask in the high bits
-    g_tn_variant = (nt_variant >> 4) & 15;  // bits 4..7: TN kernel choice
+    g_tn_variant = tn;  // bits 4..7: TN kernel choice
     nt_variant &= 15;
     g_nt_variant = nt_variant;
     return OCN_OK;
@@ -571,7 +562,6 @@ int tn_accum(const void* A, int lda, const void* B, int ldb, float* dW, int ldw,
     GemmTnArgs a;
     a.A = (const bf16*)A; a.B = (const bf16*)B; a.dW = dW; a.dbias = dbias;
     a.lda = lda; a.ldb = ldb; a.ldw = ldw; a.M = M; a.N = N; a.K = K; a.alpha = alpha; a.ablate = 0; a.nsplit = 0; a.ws = nullptr;
-    a.mf16 = tn_mf16();
     const long need = det ? ocn_tn5_workspace_bytes(M, N, K) : 0;
     if (det && need > 0) {
         OCN_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)dW & 15) == 0 && ldw % 4 == 0,
@@ -631,7 +621,6 @@ extern "C" int ocn_gemm_tn_accum2(const void* A1, int lda1, const void* B1, int 
         a.A = (const bf16*)A1; a.B = (const bf16*)B1; a.dW = dW1; a.dbias = dbias1; a.lda = lda1; a.ldb = ldb1; a.ldw = ldw1; a.N = N1;
         a.A2 = (const bf16*)A2; a.B2 = (const bf16*)B2; a.dW2 = dW2; a.dbias2 = dbias2; a.lda2 = lda2; a.ldb2 = ldb2; a.ldw2 = ldw2; a.N2 = N2;
         a.M = M; a.K = K; a.alpha = alpha; a.ablate = 0; a.nsplit = 0; a.ws = nullptr;
-        a.mf16 = tn_mf16();
         const int rc = ocn_launch_tn5_pair(a, (hipStream_t)stream);
         if (rc < 0) ocn_set_error("ocn_gemm_tn_accum2: launch failed");
         if (rc <= 0) return rc;

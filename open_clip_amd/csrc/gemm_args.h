@@ -68,7 +68,6 @@ struct GemmTnArgs {
     int lda2, ldb2, ldw2, N2, ntile1, ntile_all;
     int* rescue;  // tile-rescue board (as GemmNtArgs::rescue); a share = the `pieces` sub-chunks of a workgroup's M-chunk
     int pieces, piece_rows;
-    int mf16;  // main loop of the hand-scheduled kernel (gemm_tn5.hip): 0 = v_mfma_f32_32x32x16_bf16, 1 = v_mfma_f32_16x16x32_bf16
 };
 
 // tile rescue (core.hip): a zeroed board for ONE launch on `st` when ocn_set_tile_rescue(1) is in force and the launch has at most OCN_RESCUE_SLOTS workgroups, else null
@@ -83,5 +82,3 @@ int ocn_launch_tn5(GemmTnArgs a, hipStream_t st);
 int ocn_launch_tn5_pair(GemmTnArgs a, hipStream_t st);
 // bytes of workspace with which ocn_launch_tn5 replaces its atomic epilogue by partial tiles + a reduce pass (0: atomics are fine)
 long ocn_tn5_workspace_bytes(int M, int N, int K);
-// developer build: the main-loop clock stamps of the last stamped wgrad launch (knob 4 & 4), 1024 int64; served by ocn_debug_nt5_trace under that knob
-int ocn_tn5_debug_stamps(long long* host_out);

@@ -1117,7 +1117,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt5_kernel(GemmNtArgs a) {
 #undef DMA_B1
 }
 
-int g_num_cu = 0;
 }  // namespace
 extern int g_ocn_tuning[16];
 namespace {
@@ -1153,7 +1152,7 @@ int nt5_stagger(int ntiles, int K, int forced) {
     if (forced == 0 || forced == 63) return 0;
     if (forced != 62) return forced * 100;
     constexpr bool heavy = (EPI == OCN_EPI_BIAS_GELU || EPI == OCN_EPI_BIAS_QUICKGELU || EPI == OCN_EPI_DGELU || EPI == OCN_EPI_BIAS_RESID_F32 || EPI == OCN_EPI_BIAS_RESID_BF16 || EPI == OCN_EPI_F32);
-    if (!heavy || ntiles < 12 * g_num_cu) return 0;
+    if (!heavy || ntiles < 12 * ocn_num_cus()) return 0;
     const int tile_us = (K / 64) * 2 + 6;
     return tile_us * 100 / 4;
 }
@@ -1184,12 +1183,6 @@ int launch5_aux(GemmNtArgs a, int grid, hipStream_t st) {
 
 template <int EPI>
 int launch5(GemmNtArgs a, hipStream_t st) {
-    if (g_num_cu == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_num_cu = n;
-    }
 #ifndef OCN_DEV_BUILD
     a.ablate = 0;
 #endif
@@ -1198,7 +1191,7 @@ int launch5(GemmNtArgs a, hipStream_t st) {
     a.ntiles = ocn_cdiv(a.M, 256) * a.tiles_n * a.ksplit;  // split-K: every K-slice of every output tile is an entry of the walk
     a.band = nt5_band(a.M, a.N, a.K, (a.ablate >> 8) & 31);
     a.stagger = nt5_stagger<EPI>(a.ntiles, a.K, (a.ablate >> 13) & 63);
-    a.first_wave = g_num_cu;
+    a.first_wave = ocn_num_cus();
 #ifdef OCN_DEV_BUILD
     a.stagger_mode = g_ocn_tuning[3];
 #else
@@ -1211,7 +1204,7 @@ int launch5(GemmNtArgs a, hipStream_t st) {
     // (profiles/r01_nt5_workgroups_per_cu_sweep.txt), in the training step it costs 1.0 % (235.0 -> 237.4 ms, same box), which is
     // more than collectives that are active for ~1.5 % of a step can take back -- so k = 1 stays the default.
     const int per_cu = g_ocn_tuning[10] > 0 ? g_ocn_tuning[10] : 1;
-    const int grid = a.ntiles < g_num_cu * per_cu ? a.ntiles : g_num_cu * per_cu;
+    const int grid = a.ntiles < ocn_num_cus() * per_cu ? a.ntiles : ocn_num_cus() * per_cu;
     // The last, partial round of tiles as half tiles (see the kernel): when R = ntiles mod grid tiles are left over for at most half of the
     // workgroups, 2R workgroups compute a 128 x 256 half each -- the two halves of a tile on the same XCD (partner offset a multiple of 8).
     // Developer knob 12 = 1 (OCN_DEV_BUILD): whole tail tiles as before (A/B).
@@ -1278,7 +1271,6 @@ int launch5(GemmNtArgs a, hipStream_t st) {
 
 extern "C" int ocn_debug_nt5_trace(long long* host_out /*[1024]*/) {
 #ifdef OCN_DEV_BUILD
-    if (g_ocn_tuning[4] & 4) return ocn_tn5_debug_stamps(host_out);  // the wgrad kernel's main-loop stamps (gemm_tn5.hip)
     return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_nt5_trace), sizeof(long long) * 1024) == hipSuccess ? OCN_OK : OCN_ERR_LAUNCH;
 #else
     (void)host_out;

@@ -1,7 +1,7 @@
 // Hand-scheduled TN (weight-gradient) GEMM for gfx950:  dW[n,k] += alpha * sum_m A[m,n] * B[m,k]  (+ dbias[n] += alpha * sum_m A[m,n]).
 //
 // Same geometry as gemm_tn_ring_kernel (gemm.hip): a 256 (n) x 256 (k) tile of dW per workgroup, 8 waves (2 x 4, wave tile
-// 128 x 64 = 4 x 2 MFMA blocks), 32 reduction rows per step, 4-slot LDS ring (4 x 32 KiB: [32 m][256 n] of A and
+// 128 x 64 = 8 x 4 MFMA blocks), 32 reduction rows per step, 4-slot LDS ring (4 x 32 KiB: [32 m][256 n] of A and
 // [32 m][256 k] of B as 512-byte rows, 16-byte chunks XOR-swizzled by (row & 3) << 2 on the SOURCE address), split over M so
 // that one launch fills the chip; fp32 atomics into dW.  What changed, and why (disassembly of the ring kernel):
 //   * with compiler-visible global_load_lds + ds_read_tr builtins hipcc waits vmcnt(0) before the fragment reads of every
@@ -14,16 +14,15 @@
 //   * the bias gradient (column sums of A by an MFMA against ones) is time-sliced over the tiles_k workgroups that share an
 //     A strip: workgroup tk does it on steps kt == tk (mod tiles_k), so every workgroup carries the same 1/(8 tiles_k) extra
 //     MFMA work instead of one workgroup in tiles_k carrying 1/8.
-// Step kt (stage kt lives in ring slot kt & 3; X = fragments of sub-step 0, Y = sub-step 1):
+// Main loop on v_mfma_f32_16x16x32_bf16: the 32 reduction rows of a step are the K depth of ONE instruction, 8 x 4 blocks of 16 per wave (32 MFMAs
+// per step into 128 accumulator registers), lane group g = lane >> 4 holding reduction rows 8g..8g+7.  A 32-lane half of a fragment read takes two
+// blocks 8 rows apart, so the LDS image folds row bit 3 into the chunk swizzle: (row & 3) << 2 | (row >> 3 & 1) << 1 (SQ_LDS_BANK_CONFLICT = 0).
+// Step kt (stage kt lives in ring slot kt & 3; X = A blocks 0..3 of the stage, Y = A blocks 4..7, both against its four B blocks):
 //   wait vmcnt(4) [own DMAs of stage kt+1 landed] -> s_barrier [everybody's landed; everybody finished reading stage kt-1]
-//   issue reads Y(kt) | 8 MFMAs on X(kt) with the 4 DMA pieces of stage kt+3 (into the slot of stage kt-1) between them
-//   wait lgkmcnt(0) | issue reads X(kt+1) | 8 MFMAs on Y(kt) | wait lgkmcnt(0)
-// Two main loops behind one template parameter (MF16), same geometry, ring, DMA pattern, vmcnt(4) and barrier: v_mfma_f32_32x32x16_bf16 as above
-// (two 16-row sub-steps per step), and v_mfma_f32_16x16x32_bf16 -- 32 reduction rows are the K depth of ONE instruction, 8 x 4 blocks of 16 per
-// wave, lane group g = lane >> 4 holding reduction rows 8g..8g+7; its LDS image folds row bit 3 into the chunk swizzle, (row & 3) << 2 | (row >> 3 & 1)
-// << 1, because a 32-lane half reads two blocks 8 rows apart (SQ_LDS_BANK_CONFLICT = 0 on both images).  The socket is power-limited under
-// this kernel and holds a 2-11 % higher clock on the 16x16x32 loop (out-proj + QKV pair: 1.56 -> 1.66 GHz inside the loop; -3.7 % per launch, -1.5 % on the step:
-// profiles/tn5_mfma_shape.json), so that form is the default; ocn_set_gemm_variant's TN values 6 / 7 select either (tools/ab_tn_mfma_shape.py).
+//   issue reads Y(kt) | 16 MFMAs on X(kt), B block by B block, with the 4 DMA pieces of stage kt+3 (into the slot of stage kt-1) between them
+//   wait lgkmcnt(0) | issue reads X(kt+1) | 16 MFMAs on Y(kt), each B block re-read for stage kt+1 behind its 4 | wait for X(kt+1) and B blocks 0, 1
+// The socket is power-limited under this kernel and holds a 2-11 % higher clock on this loop than on the v_mfma_f32_32x32x16_bf16 loop it replaced
+// (faster on every wgrad launch, -1.5 % on the step: profiles/tn5_mfma_shape.json).
 #include "gemm_args.h"
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
@@ -38,9 +37,6 @@ constexpr int STAGE = 32768, HALF = 16384, LDS_BYTES = 4 * STAGE;
 struct Frag {
     u32x2 lo, hi;  // m rows {0..3} and {4..7} of this lane's 8 reduction slots
 };
-struct FragSet {
-    Frag a[4], b[2];
-};
 
 OCN_DEV bf16x8 cat(const Frag& f) {
     const u32x4 v = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
@@ -48,32 +44,18 @@ OCN_DEV bf16x8 cat(const Frag& f) {
 }
 
 #define SB() __builtin_amdgcn_sched_barrier(0)
-// two transposing reads (rows r..r+3 and r+4..r+7) of one 32-wide block; early-clobber: the address is read twice
+// two transposing reads (rows r..r+3 and r+4..r+7) of one 16-wide block; early-clobber: the address is read twice
 #define TRR(F, ADDR, OFF)                                                                              \
     asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4"          \
                  : "=&v"((F).lo), "=&v"((F).hi)                                                        \
                  : "v"(ADDR), "i"(OFF), "i"((OFF) + 2048))
-// the wait names every destination "+v": the compiler cannot copy / combine a fragment before its data has landed
-#define WAIT_SET(S)                                                                                                      \
-    asm volatile("s_waitcnt lgkmcnt(0)"                                                                                  \
-                 : "+v"((S).a[0].lo), "+v"((S).a[0].hi), "+v"((S).a[1].lo), "+v"((S).a[1].hi), "+v"((S).a[2].lo),          \
-                   "+v"((S).a[2].hi), "+v"((S).a[3].lo), "+v"((S).a[3].hi), "+v"((S).b[0].lo), "+v"((S).b[0].hi),          \
-                   "+v"((S).b[1].lo), "+v"((S).b[1].hi))
 
 // RESCUE (ocn_set_tile_rescue, the multi-GPU form; protocol: gemm_nt5.hip): a workgroup's share is its M-chunk in a.pieces pieces of a.piece_rows rows.
 // The owner adds RESCUE_BIG to its counter when it starts and takes the chunk from the first piece no finisher has claimed to the end (one epilogue);
 // a finisher claims ONE piece of a chunk nobody has started and adds its partial tile with the same fp32 atomics.  The bias slices stay consistent:
 // step s of a chunk (counted from the chunk's first row) belongs to the workgroup with tk == s (mod tiles_k), whoever computes it.
 constexpr int RESCUE_BIG = 1 << 20;
-#ifdef OCN_DEV_BUILD
-// developer build, knob 4 & 4: workgroup w < 512 leaves {delta s_memtime (shader clocks), delta s_memrealtime (100 MHz ticks)} around its main loop
-// here -- the clock the loop held is their ratio (tools/ab_tn_mfma_shape.py --stamps).  Nothing else reads it; the product library has no stamp.
-__device__ long long g_tn5_stamp[1024];
-#endif
-// MF16: the main loop on v_mfma_f32_16x16x32_bf16 (one step = the K depth of one instruction: 8 n-blocks x 4 k-blocks of 16 per wave, 32 MFMAs
-// where the other form issues 16 of 32x32x16; the same 128 accumulator registers, the same 24 transposing reads per wave and step).  The two forms
-// differ in the LDS image (chunk swizzle below), the fragment reads, the accumulator -> (n, k) map of the epilogues and nothing else.
-template <bool BIAS, bool RESCUE = false, bool MF16 = false>
+template <bool BIAS, bool RESCUE>
 __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -135,9 +117,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int r = (wave + j * 8) * 2 + (lane >> 5);
-        // source-side chunk swizzle.  MF16: a 32-lane half of a fragment read takes two 4 x 16 blocks 8 rows apart in the same columns; row
+        // source-side chunk swizzle: a 32-lane half of a fragment read takes two 4 x 16 blocks 8 rows apart in the same columns; row
         // bit 3 folded into chunk bit 1 (an 8-bank shift) keeps them on different banks
-        const int c = ((lane & 31) ^ (((r & 3) << 2) | (MF16 ? ((r >> 3) & 1) << 1 : 0))) * 8;
+        const int c = ((lane & 31) ^ (((r & 3) << 2) | ((r >> 3) & 1) << 1)) * 8;
         voA[j] = (n0 + c) < a.N ? (unsigned)(r * a.lda + n0 + c) * 2u : 0x80000000u;  // out-of-range columns stay out of range
         voB[j] = (k0 + c) < a.K ? (unsigned)(r * a.ldb + k0 + c) * 2u : 0x80000000u;
     }
@@ -163,14 +145,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
     }
 
     // ---- fragment read addresses -----------------------------------------------------------------------------------------
-    // 16-lane group: 4 rows x 16 columns; lane i passes the address of columns (i&3)*4.. of row i>>2 and receives column i.
-    // byte = row * 512 + (chunk ^ ((row & 3) << 2)) * 16 + (i & 1) * 8, row = s*16 + h*8 + (i>>2) (+4), chunk = col/8 + (i&3)>>1.
-    // acc index ib of this wave is A block (ib + wk) & 3 (so that block wk, the one this wave sums for dbias, is a[0]).
-    // MF16: lane group gg = lane >> 4 takes reduction rows 8 gg .. 8 gg + 3 (+4) of the stage, every group the same 16 columns:
+    // 16-lane group: 4 rows x 16 columns; lane i passes the address of columns (i&3)*4.. of row i>>2 and receives column i.  Lane group
+    // gg = lane >> 4 takes reduction rows 8 gg .. 8 gg + 3 (+4) of the stage, every group the same 16 columns:
     // byte = row * 512 + (chunk ^ ((row & 3) << 2 | (row >> 3 & 1) << 1)) * 16 + (i & 1) * 8, row = gg*8 + (i>>2) (+4), chunk = col/8 + (i&3)>>1.
-    // acc index ib is A block (ib + 2 wk) & 7: blocks 2 wk, 2 wk + 1 -- the ones this wave sums for dbias -- are ib 0, 1.
-    unsigned vaL[8], vbL[4], vaH[8], vbH[4];  // ring slots 0-1 / 2-3 (ds offsets are 16 bits); the 32x32x16 form uses the first 4 / 2
-    if constexpr (MF16) {
+    // acc index ib of this wave is A block (ib + 2 wk) & 7: blocks 2 wk, 2 wk + 1 -- the ones this wave sums for dbias -- are ib 0, 1.
+    unsigned vaL[8], vbL[4], vaH[8], vbH[4];  // ring slots 0-1 / 2-3 (ds offsets are 16 bits)
+    {
         const int i = lane & 15, gg = lane >> 4, q = i >> 2;
         const unsigned sw = (unsigned)((q << 2) | ((gg & 1) << 1));
         const unsigned lane_off = (unsigned)((gg * 8 + q) * 512 + ((i & 3) >> 1) * 16 + (i & 1) * 8);
@@ -185,33 +165,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
             vbL[jb] = lds_base + lane_off + ((unsigned)(wk * 8 + 2 * jb) ^ sw) * 16;
             vbH[jb] = vbL[jb] + 65536u;
         }
-    } else {
-        const int i = lane & 15, g = (lane >> 4) & 1, h = lane >> 5, i2 = i >> 2;
-        const unsigned lane_off = (unsigned)((h * 8 + i2) * 512 + (2 * g + ((i & 3) >> 1)) * 16 + (i & 1) * 8);
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) {
-            const int blk = (ib + wk) & 3;
-            vaL[ib] = lds_base + lane_off + (unsigned)((wn * 16 + ((blk ^ i2) << 2)) * 16);
-            vaH[ib] = vaL[ib] + 65536u;
-        }
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-            vbL[jb] = lds_base + lane_off + (unsigned)((((wk * 2 + jb) ^ i2) << 2) * 16);
-            vbH[jb] = vbL[jb] + 65536u;
-        }
     }
-#define READ_SET(S, SLOT, SUB)                                                                       \
-    {                                                                                                \
-        constexpr int o_ = ((SLOT) & 1) * STAGE + (SUB) * 8192;                                       \
-        TRR((S).a[0], ((SLOT) < 2 ? vaL[0] : vaH[0]), o_);                                            \
-        TRR((S).b[0], ((SLOT) < 2 ? vbL[0] : vbH[0]), o_ + HALF);                                     \
-        TRR((S).b[1], ((SLOT) < 2 ? vbL[1] : vbH[1]), o_ + HALF);                                     \
-        TRR((S).a[1], ((SLOT) < 2 ? vaL[1] : vaH[1]), o_);                                            \
-        TRR((S).a[2], ((SLOT) < 2 ? vaL[2] : vaH[2]), o_);                                            \
-        TRR((S).a[3], ((SLOT) < 2 ? vaL[3] : vaH[3]), o_);                                            \
-    }
-
-#define READ_A16(F, IB0, SLOT)                                                                     \
+#define READ_A(F, IB0, SLOT)                                                                \
     {                                                                                                \
         constexpr int o_ = ((SLOT) & 1) * STAGE;                                                      \
         TRR((F)[0], ((SLOT) < 2 ? vaL[(IB0) + 0] : vaH[(IB0) + 0]), o_);                              \
@@ -219,37 +174,29 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
         TRR((F)[2], ((SLOT) < 2 ? vaL[(IB0) + 2] : vaH[(IB0) + 2]), o_);                              \
         TRR((F)[3], ((SLOT) < 2 ? vaL[(IB0) + 3] : vaH[(IB0) + 3]), o_);                              \
     }
-#define READ_B16(JB, SLOT) TRR(bb[JB], ((SLOT) < 2 ? vbL[JB] : vbH[JB]), ((SLOT) & 1) * STAGE + HALF);
-#define WAIT_Y16()                                                                                                       \
+#define READ_B(JB, SLOT) TRR(bb[JB], ((SLOT) < 2 ? vbL[JB] : vbH[JB]), ((SLOT) & 1) * STAGE + HALF);
+// a wait names every destination "+v": the compiler cannot copy / combine a fragment before its data has landed
+#define WAIT_Y()                                                                                                     \
     asm volatile("s_waitcnt lgkmcnt(0)"                                                                                  \
                  : "+v"(ya[0].lo), "+v"(ya[0].hi), "+v"(ya[1].lo), "+v"(ya[1].hi), "+v"(ya[2].lo), "+v"(ya[2].hi), "+v"(ya[3].lo), "+v"(ya[3].hi))
 // LDS reads return in order and nothing else in the loop counts on lgkmcnt: a counted wait leaves the LAST reads issued in flight.
 // X and B blocks 0, 1 of the next step (its B blocks 2, 3 -- 4 reads -- may still be in flight) / everything / B blocks 2, 3 (behind them: the 8 reads of Y)
-#define WAIT_XB01_16()                                                                                                   \
+#define WAIT_XB01()                                                                                                   \
     asm volatile("s_waitcnt lgkmcnt(4)"                                                                                  \
                  : "+v"(xa[0].lo), "+v"(xa[0].hi), "+v"(xa[1].lo), "+v"(xa[1].hi), "+v"(xa[2].lo), "+v"(xa[2].hi), "+v"(xa[3].lo), "+v"(xa[3].hi), \
                    "+v"(bb[0].lo), "+v"(bb[0].hi), "+v"(bb[1].lo), "+v"(bb[1].hi))
-#define WAIT_XB_16()                                                                                                     \
+#define WAIT_XB()                                                                                                     \
     asm volatile("s_waitcnt lgkmcnt(0)"                                                                                  \
                  : "+v"(xa[0].lo), "+v"(xa[0].hi), "+v"(xa[1].lo), "+v"(xa[1].hi), "+v"(xa[2].lo), "+v"(xa[2].hi), "+v"(xa[3].lo), "+v"(xa[3].hi), \
                    "+v"(bb[0].lo), "+v"(bb[0].hi), "+v"(bb[1].lo), "+v"(bb[1].hi), "+v"(bb[2].lo), "+v"(bb[2].hi), "+v"(bb[3].lo), "+v"(bb[3].hi))
-#define WAIT_B23_16() asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(bb[2].lo), "+v"(bb[2].hi), "+v"(bb[3].lo), "+v"(bb[3].hi))
+#define WAIT_B23() asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(bb[2].lo), "+v"(bb[2].hi), "+v"(bb[3].lo), "+v"(bb[3].hi))
 
-    f32x16 acc[4][2], accb;
-    f32x4 acc16[8][4], accb16[2];  // MF16
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accb[r] = 0.f;
+    f32x4 acc[8][4], accb[2];  // [A block ib][B block jb] of 16 x 16; the ones-products of A blocks ib 0, 1
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc16[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    accb16[0] = accb16[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    accb[0] = accb[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
     bf16x8 ones;
 #pragma unroll
     for (int e = 0; e < 8; ++e) ones[e] = (bf16)1.0f;
@@ -266,8 +213,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
     DMA_ADV()
     DMA_A(0, 2) DMA_A(1, 2) DMA_B(0, 2) DMA_B(1, 2)
     DMA_ADV()
-    FragSet X, Y;
-    Frag xa[4], ya[4], bb[4];  // MF16: A blocks ib 0..3 / 4..7 of a stage and its four B blocks
+    Frag xa[4], ya[4], bb[4];  // A blocks ib 0..3 / 4..7 of a stage and its four B blocks
 #if (OCN_PRIO_MODE & 2)
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
 #endif
@@ -284,20 +230,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
             continue;
         }
     }
-#ifdef OCN_DEV_BUILD
-    const long long st_clk = clock64(), st_wall = wall_clock64();  // (in front of the first fragment read: its lgkmcnt(0) retires them)
-#endif
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     SB();
-    if constexpr (MF16) {
-        READ_A16(xa, 0, 0)
-        READ_B16(0, 0) READ_B16(1, 0) READ_B16(2, 0) READ_B16(3, 0)
-        WAIT_XB_16();
-    } else {
-        READ_SET(X, 0, 0)
-        WAIT_SET(X);
-    }
+    READ_A(xa, 0, 0)
+    READ_B(0, 0) READ_B(1, 0) READ_B(2, 0) READ_B(3, 0)
+    WAIT_XB();
     SB();
 
 // OCN_PRIO_MODE (compile-time experiment, profiles/r02_setprio_experiment.txt): 1 = s_setprio 1 over the MFMA work of a step,
@@ -312,65 +250,23 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
 #define PRIO_ON()
 #define PRIO_OFF()
 #endif
-#define MM(S, IB, JB) acc[IB][JB] = mfma32(cat((S).a[IB]), cat((S).b[JB]), acc[IB][JB]);
-#define STEP(SLOT)                                                                                   \
-    {                                                                                                \
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                             \
-        __builtin_amdgcn_s_barrier();                                                                \
-        SB();                                                                                        \
-        READ_SET(Y, SLOT, 1)                                                                         \
-        SB(); PRIO_ON()                                                                              \
-        const bool bias_now = BIAS && (bc == 0);                                                     \
-        MM(X, 0, 0) MM(X, 0, 1)                                                                      \
-        SB();                                                                                        \
-        DMA_A(0, ((SLOT) + 3) & 3)                                                                   \
-        SB();                                                                                        \
-        MM(X, 1, 0) MM(X, 1, 1)                                                                      \
-        SB();                                                                                        \
-        DMA_A(1, ((SLOT) + 3) & 3)                                                                   \
-        SB();                                                                                        \
-        MM(X, 2, 0) MM(X, 2, 1)                                                                      \
-        SB();                                                                                        \
-        DMA_B(0, ((SLOT) + 3) & 3)                                                                   \
-        SB();                                                                                        \
-        MM(X, 3, 0) MM(X, 3, 1)                                                                      \
-        SB();                                                                                        \
-        DMA_B(1, ((SLOT) + 3) & 3)                                                                   \
-        if (bias_now) accb = mfma32(cat(X.a[0]), ones, accb);                                        \
-        PRIO_OFF() SB();                                                                             \
-        WAIT_SET(Y);                                                                                 \
-        SB();                                                                                        \
-        READ_SET(X, ((SLOT) + 1) & 3, 0)                                                             \
-        SB(); PRIO_ON()                                                                              \
-        MM(Y, 0, 0) MM(Y, 0, 1) MM(Y, 1, 0) MM(Y, 1, 1)                                              \
-        DMA_ADV()                                                                                    \
-        MM(Y, 2, 0) MM(Y, 2, 1) MM(Y, 3, 0) MM(Y, 3, 1)                                              \
-        if (bias_now) accb = mfma32(cat(Y.a[0]), ones, accb);                                        \
-        if (BIAS) bc = (bc == 0 ? a.tiles_k : bc) - 1;                                               \
-        PRIO_OFF() SB();                                                                             \
-        WAIT_SET(X);                                                                                 \
-        SB();                                                                                        \
-    }
-// MF16 step: X = A blocks ib 0..3, Y = A blocks ib 4..7 of the same stage, both against its four B blocks (one copy: each is re-read for the
-// next stage as soon as Y's MFMAs on it are issued).  LAST: the step before the loop's back edge leaves no read in flight.
-//   wait vmcnt(4) -> s_barrier | issue reads Y(kt) | 16 MFMAs on X(kt), B block by B block (blocks 2, 3 awaited behind the first 8), with the 4 DMA
-//   pieces of stage kt+3 between them | wait lgkmcnt(0) | issue reads X(kt+1) | 16 MFMAs on Y(kt), each B block re-read behind its 4 |
-//   wait for X(kt+1) and B blocks 0, 1
-#define MM16(AF, IB, JB) acc16[IB][JB] = mfma16(cat(AF), cat(bb[JB]), acc16[IB][JB]);
-#define MMCOL(F, IB0, JB) MM16((F)[0], (IB0) + 0, JB) MM16((F)[1], (IB0) + 1, JB) MM16((F)[2], (IB0) + 2, JB) MM16((F)[3], (IB0) + 3, JB)
+// One step (the header has its outline): the four B blocks exist in one copy, each re-read for the next stage as soon as Y's MFMAs on it are
+// issued; B blocks 2, 3 are awaited behind the first 8 MFMAs on X.  LAST: the step before the loop's back edge leaves no read in flight.
+#define MM(AF, IB, JB) acc[IB][JB] = mfma16(cat(AF), cat(bb[JB]), acc[IB][JB]);
+#define MMCOL(F, IB0, JB) MM((F)[0], (IB0) + 0, JB) MM((F)[1], (IB0) + 1, JB) MM((F)[2], (IB0) + 2, JB) MM((F)[3], (IB0) + 3, JB)
 // the bias step's two ones-products, skipped by a branch INSIDE the asm (bc is wave-uniform): a compiler-visible branch here splits the step into
 // blocks, and the register allocator then spills fragment addresses and an accumulator (42 VGPRs) where straight-line code needs 226
-#define BIAS16()                                                                                                                        \
+#define BIAS_MM()                                                                                                                        \
     asm volatile("s_cmp_lg_u32 %5, 0\n\ts_cbranch_scc1 1f\n\ts_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %2, %4, %0\n\tv_mfma_f32_16x16x32_bf16 %1, %3, %4, %1\n1:" \
-                 : "+v"(accb16[0]), "+v"(accb16[1])                                                                                      \
+                 : "+v"(accb[0]), "+v"(accb[1])                                                                                      \
                  : "v"(cat(xa[0])), "v"(cat(xa[1])), "v"(ones), "s"(__builtin_amdgcn_readfirstlane(bc))                                  \
                  : "scc");
-#define STEP16(SLOT, LAST)                                                                           \
+#define STEP(SLOT, LAST)                                                                           \
     {                                                                                                \
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");                                             \
         __builtin_amdgcn_s_barrier();                                                                \
         SB();                                                                                        \
-        READ_A16(ya, 4, SLOT)                                                                        \
+        READ_A(ya, 4, SLOT)                                                                        \
         SB(); PRIO_ON()                                                                              \
         MMCOL(xa, 0, 0)                                                                              \
         SB();                                                                                        \
@@ -380,7 +276,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
         SB();                                                                                        \
         DMA_A(1, ((SLOT) + 3) & 3)                                                                   \
         SB();                                                                                        \
-        WAIT_B23_16();                                                                               \
+        WAIT_B23();                                                                               \
         SB();                                                                                        \
         MMCOL(xa, 0, 2)                                                                              \
         SB();                                                                                        \
@@ -389,115 +285,76 @@ __global__ __launch_bounds__(512, 2) void gemm_tn5_kernel(GemmTnArgs a_in) {
         MMCOL(xa, 0, 3)                                                                              \
         SB();                                                                                        \
         DMA_B(1, ((SLOT) + 3) & 3)                                                                   \
-        if (BIAS) BIAS16()                                                                           \
+        if (BIAS) BIAS_MM()                                                                           \
         PRIO_OFF() SB();                                                                             \
-        WAIT_Y16();                                                                                  \
+        WAIT_Y();                                                                                  \
         SB();                                                                                        \
-        READ_A16(xa, 0, ((SLOT) + 1) & 3)                                                            \
+        READ_A(xa, 0, ((SLOT) + 1) & 3)                                                            \
         SB(); PRIO_ON()                                                                              \
         MMCOL(ya, 4, 0)                                                                              \
         SB();                                                                                        \
-        READ_B16(0, ((SLOT) + 1) & 3)                                                                \
+        READ_B(0, ((SLOT) + 1) & 3)                                                                \
         SB();                                                                                        \
         MMCOL(ya, 4, 1)                                                                              \
         SB();                                                                                        \
-        READ_B16(1, ((SLOT) + 1) & 3)                                                                \
+        READ_B(1, ((SLOT) + 1) & 3)                                                                \
         DMA_ADV()                                                                                    \
         SB();                                                                                        \
         MMCOL(ya, 4, 2)                                                                              \
         SB();                                                                                        \
-        READ_B16(2, ((SLOT) + 1) & 3)                                                                \
+        READ_B(2, ((SLOT) + 1) & 3)                                                                \
         SB();                                                                                        \
         MMCOL(ya, 4, 3)                                                                              \
         SB();                                                                                        \
-        READ_B16(3, ((SLOT) + 1) & 3)                                                                \
+        READ_B(3, ((SLOT) + 1) & 3)                                                                \
         if (BIAS) bc = (bc == 0 ? a.tiles_k : bc) - 1;                                               \
         PRIO_OFF() SB();                                                                             \
-        if (LAST) WAIT_XB_16(); else WAIT_XB01_16();                                                 \
+        if (LAST) WAIT_XB(); else WAIT_XB01();                                                 \
         SB();                                                                                        \
     }
     // nk is rounded up to whole groups of 4 steps: the surplus steps see all-zero stages (reads past the split's last row)
-    if constexpr (MF16) {
-        for (int kt = 0; kt < nk; kt += 4) {
-            STEP16(0, false)
-            STEP16(1, false)
-            STEP16(2, false)
-            STEP16(3, true)
-        }
-    } else {
-        for (int kt = 0; kt < nk; kt += 4) {
-            STEP(0)
-            STEP(1)
-            STEP(2)
-            STEP(3)
-        }
+    for (int kt = 0; kt < nk; kt += 4) {
+        STEP(0, false)
+        STEP(1, false)
+        STEP(2, false)
+        STEP(3, true)
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (zero-fill) DMAs must land before the LDS is released
-#ifdef OCN_DEV_BUILD
-    if ((a.ablate & 4) && threadIdx.x == 0 && blockIdx.x < 512) {
-        g_tn5_stamp[blockIdx.x * 2] = clock64() - st_clk;
-        g_tn5_stamp[blockIdx.x * 2 + 1] = wall_clock64() - st_wall;
-    }
-#endif
 #undef STEP
-#undef STEP16
 #undef MM
-#undef MM16
 #undef MMCOL
-#undef BIAS16
-#undef READ_SET
-#undef READ_A16
-#undef READ_B16
-#undef WAIT_Y16
-#undef WAIT_XB_16
-#undef WAIT_XB01_16
-#undef WAIT_B23_16
+#undef BIAS_MM
+#undef READ_A
+#undef READ_B
+#undef WAIT_Y
+#undef WAIT_XB
+#undef WAIT_XB01
+#undef WAIT_B23
 #undef DMA_ADV
 #undef DMA_A
 #undef DMA_B
 #undef DMA
 
-    // ---- epilogue: fp32 atomics.  32x32x16: lanes of a half-wave hit 32 consecutive k = one 128-byte line of one n row; 16x16x32: a 16-lane
-    // group hits 16 consecutive k (64 bytes) of 4 different n rows -------------------------------------------------------------------------
+    // ---- epilogue: fp32 atomics; a 16-lane group hits 16 consecutive k (64 bytes) of 4 different n rows ---------------------------------
     // f(n, k, value) for every accumulator element of this lane / g(n, value) for its bias sums (the lanes that hold column 0 of the ones-product)
     auto each_acc = [&](auto&& f) __attribute__((always_inline)) {
-        if constexpr (MF16) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int blk = (i + 2 * wk) & 7;
+        for (int i = 0; i < 8; ++i) {
+            const int blk = (i + 2 * wk) & 7;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int gk = k0 + wk * 64 + j * 16 + (lane & 15);
+            for (int j = 0; j < 4; ++j) {
+                const int gk = k0 + wk * 64 + j * 16 + (lane & 15);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) f(n0 + wn * 128 + blk * 16 + mfma16_row(r, lane), gk, acc16[i][j][r]);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int blk = (i + wk) & 3;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int gk = k0 + wk * 64 + j * 32 + (lane & 31);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) f(n0 + wn * 128 + blk * 32 + mfma32_row(r, lane), gk, acc[i][j][r]);
-                }
+                for (int r = 0; r < 4; ++r) f(n0 + wn * 128 + blk * 16 + mfma16_row(r, lane), gk, acc[i][j][r]);
             }
         }
     };
     auto each_bias = [&](auto&& g) __attribute__((always_inline)) {
-        if constexpr (MF16) {
-            if ((lane & 15) == 0) {
+        if ((lane & 15) == 0) {
 #pragma unroll
-                for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) g(n0 + wn * 128 + (2 * wk + t) * 16 + mfma16_row(r, lane), accb16[t][r]);
-            }
-        } else {
-            if ((lane & 31) == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) g(n0 + wn * 128 + wk * 32 + mfma32_row(r, lane), accb[r]);
-            }
+                for (int r = 0; r < 4; ++r) g(n0 + wn * 128 + (2 * wk + t) * 16 + mfma16_row(r, lane), accb[t][r]);
         }
     };
     if constexpr (!RESCUE) {
@@ -585,8 +442,6 @@ __global__ __launch_bounds__(256) void tn5_reduce_kernel(const float* __restrict
     }
 }
 
-int g_tn5_num_cu = 0;
-
 int tn5_splits(int M, int N, int K, int num_cu, int over) {
     const int ntile = ocn_cdiv(N, 256) * ocn_cdiv(K, 256);
     const int msteps = ocn_cdiv(M, 32);
@@ -602,75 +457,41 @@ int tn5_splits(int M, int N, int K, int num_cu, int over) {
 extern int g_ocn_tuning[16];
 
 // Static launch, or -- ocn_set_tile_rescue(1), atomic epilogue only -- the rescue form: every M-chunk in up to 8 pieces of whole 128-row step groups
-template <bool BIAS, bool RESCUE, bool MF16>
+template <bool BIAS, bool RESCUE>
 static void tn5_launch_as(const GemmTnArgs& a, hipStream_t st) {
     constexpr int lds = LDS_BYTES + (RESCUE ? 64 : 0);
     static bool attr_set = false;  // (one per instantiation)
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)gemm_tn5_kernel<BIAS, RESCUE, MF16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        (void)hipFuncSetAttribute((const void*)gemm_tn5_kernel<BIAS, RESCUE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         attr_set = true;
     }
-    hipLaunchKernelGGL((gemm_tn5_kernel<BIAS, RESCUE, MF16>), dim3(a.nwg), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((gemm_tn5_kernel<BIAS, RESCUE>), dim3(a.nwg), dim3(512), lds, st, a);
 }
 static void tn5_launch(GemmTnArgs& a, hipStream_t st) {
     a.rescue = (a.ws || a.ablate || a.nwg < 2) ? nullptr : ocn_rescue_board(st, a.nwg);
     a.piece_rows = ocn_cdiv(ocn_cdiv(a.chunk, 8), 128) * 128;
     a.pieces = ocn_cdiv(a.chunk, a.piece_rows);
-    const int which = (a.dbias ? 4 : 0) | (a.rescue ? 2 : 0) | (a.mf16 ? 1 : 0);
-    switch (which) {
-        case 0: tn5_launch_as<false, false, false>(a, st); break;
-        case 1: tn5_launch_as<false, false, true>(a, st); break;
-        case 2: tn5_launch_as<false, true, false>(a, st); break;
-        case 3: tn5_launch_as<false, true, true>(a, st); break;
-        case 4: tn5_launch_as<true, false, false>(a, st); break;
-        case 5: tn5_launch_as<true, false, true>(a, st); break;
-        case 6: tn5_launch_as<true, true, false>(a, st); break;
-        default: tn5_launch_as<true, true, true>(a, st); break;
-    }
-}
-
-int ocn_tn5_debug_stamps(long long* host_out) {
-#ifdef OCN_DEV_BUILD
-    return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_tn5_stamp), sizeof(long long) * 1024) == hipSuccess ? OCN_OK : OCN_ERR_LAUNCH;
-#else
-    (void)host_out;
-    return OCN_ERR_INVALID;
-#endif
-}
-
-static int tn5_cus() {
-    if (g_tn5_num_cu == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_tn5_num_cu = n;
-    }
-    return g_tn5_num_cu;
+    if (a.dbias) a.rescue ? tn5_launch_as<true, true>(a, st) : tn5_launch_as<true, false>(a, st);
+    else a.rescue ? tn5_launch_as<false, true>(a, st) : tn5_launch_as<false, false>(a, st);
 }
 
 // scratch of the reproducible launch: one fp32 slab of dW per M-split + one bias row per (split, k-tile); 0 = shape not taken by this
 // kernel (the caller uses the general kernel with one split)
 long ocn_tn5_workspace_bytes(int M, int N, int K) {
     if (N % 8 || K % 8 || (long)M * N * K < (1L << 31) || N < 256 || K < 256) return 0;
-    const int splits = tn5_splits(M, N, K, tn5_cus(), 1);
+    const int splits = tn5_splits(M, N, K, ocn_num_cus(), 1);
     return ((long)splits * N * K + (long)splits * ocn_cdiv(K, 256) * N) * 4;
 }
 
 int ocn_launch_tn5(GemmTnArgs a, hipStream_t st) {
     if (a.N % 8 || a.K % 8 || a.lda % 8 || a.ldb % 8) return 1;
-    if (g_tn5_num_cu == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_tn5_num_cu = n;
-    }
     a.ablate = g_ocn_tuning[4];
     a.tiles_n = ocn_cdiv(a.N, 256);
     a.tiles_k = ocn_cdiv(a.K, 256);
     const int ntile = a.tiles_n * a.tiles_k;
     const int msteps = ocn_cdiv(a.M, 32);
     // developer knob 15 = n: size the grid for n CUs (a stream restricted to a CU subset, tools/cu_mask_probe.py)
-    const int cus = (g_ocn_tuning[15] > 0 && g_ocn_tuning[15] < g_tn5_num_cu) ? g_ocn_tuning[15] : g_tn5_num_cu;
+    const int cus = (g_ocn_tuning[15] > 0 && g_ocn_tuning[15] < ocn_num_cus()) ? g_ocn_tuning[15] : ocn_num_cus();
     int splits = cus / ntile;  // one workgroup per CU ...
     // ... developer knob 11 = k: k per CU when the M-chunks stay long (<= 10 splits).  A workgroup that starts late because its CU
     // is held by another stream's kernel then costs 1/k as much (one CU held: +43 % at k = 1, +7 % at k = 2;
@@ -711,12 +532,6 @@ int ocn_launch_tn5(GemmTnArgs a, hipStream_t st) {
 int ocn_launch_tn5_pair(GemmTnArgs a, hipStream_t st) {
     if (a.N % 8 || a.N2 % 8 || a.K % 8 || a.lda % 8 || a.ldb % 8 || a.lda2 % 8 || a.ldb2 % 8) return 1;
     if ((a.dbias == nullptr) != (a.dbias2 == nullptr)) return 1;  // one kernel instantiation serves both problems
-    if (g_tn5_num_cu == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_tn5_num_cu = n;
-    }
     a.ablate = g_ocn_tuning[4];
     a.ws = nullptr;
     a.tiles_k = ocn_cdiv(a.K, 256);
@@ -724,7 +539,7 @@ int ocn_launch_tn5_pair(GemmTnArgs a, hipStream_t st) {
     a.ntile1 = a.tiles_n * a.tiles_k;
     a.ntile_all = a.ntile1 + ocn_cdiv(a.N2, 256) * a.tiles_k;
     const int msteps = ocn_cdiv(a.M, 32);
-    int splits = g_tn5_num_cu / a.ntile_all;
+    int splits = ocn_num_cus() / a.ntile_all;
     if (splits < 1) splits = 1;
     if (splits > msteps) splits = msteps;
     a.chunk = ocn_cdiv(msteps, splits) * 32;

@@ -11,6 +11,8 @@
 
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
+#include <type_traits>
+
 extern int g_ocn_tuning[16];
 namespace {
 
@@ -25,10 +27,10 @@ OCN_DEV f32x4 ld4(const void* base, size_t idx) {
     }
 }
 
-// NTX: x (read again only by the backward, a whole forward later) is loaded with the non-temporal policy: 100 -> 89 us on the packed
+// An fp32 x (read again only by the backward, a whole forward later) is loaded with the non-temporal policy: 100 -> 89 us on the packed
 // text rows, nothing on the image rows (profiles/r03_layernorm_forward_variants.txt; fetching gamma / beta once per wave before the row
-// loop instead of per row was 3-10 % slower there and is gone).
-template <int NV, bool NTX, bool X16>
+// loop instead of per row was 3-10 % slower there and is gone); a bf16 x keeps the default policy.
+template <int NV, bool X16>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ b, bf16* __restrict__ y16,
                                                       float* __restrict__ y32, float* __restrict__ mean,
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const int c = (i * 64 + lane) * 4;
-            if (c < C) v[i] = ld4<X16, NTX>(x, (size_t)row * C + c);
+            if (c < C) v[i] = ld4<X16, !X16>(x, (size_t)row * C + c);
             else v[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
             s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
         }
@@ -81,9 +83,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const void* __restrict__ x,
     }
 }
 
-// NT: x and the residual gradient (read once, long after they were written) are loaded and the fp32 dx (read again only by the
+// Backward.  x and the residual gradient (read once, long after they were written) are loaded and the fp32 dx (read again only by the
 // next LayerNorm backward, two GEMMs later) is stored with the non-temporal policy; dy and the bf16 dx, which the neighbouring
-// GEMMs produce / consume right away, keep the default one.
+// GEMMs produce / consume right away, keep the default one (profiles/r01_ln_bwd_cache_policy.txt).
 // Workgroups of BW = 16 waves (12 for C <= 1280, 8 beyond: registers), ONE per CU, rows grid-strided: the dgamma / dbeta partials of a workgroup's waves
 // are folded through LDS (a tree, BW / 2 slabs) and leave as one fp32 atomic per column per WORKGROUP -- with 2048 four-wave workgroups
 // the 2048-way contended atomics were 0.06-0.17 ms of a 0.37-0.52 ms launch (profiles/r02_layernorm_grid.txt).
@@ -95,8 +97,9 @@ constexpr int ln_bwd_waves() { return NV <= 3 ? 16 : (NV <= 5 ? 12 : 8); }  // w
 // (transformer.py:246, :299) -- summed from fp32 values instead of from the bf16 operand of the weight-gradient GEMM: bias gradients are column
 // sums with heavy cancellation across a contrastive batch, and at batch 4096 the rounding of the summands alone put them at 1.0 of their
 // parity bound (profiles/r04_parity_report.txt).
+
 // X16 / DR16: x resp. the residual gradient are bf16 (the image tower's bf16 residual stream, see the header)
-template <int NV, bool DY32, bool NT, bool CS, bool X16 = false, bool DR16 = false>
+template <int NV, bool DY32, bool CS, bool X16 = false, bool DR16 = false>
 __global__ __launch_bounds__(ln_bwd_waves<NV>() * 64) void ln_bwd_kernel(const void* __restrict__ dyv, const void* __restrict__ x,
                                                       const float* __restrict__ w, const float* __restrict__ mean,
                                                       const float* __restrict__ rstd, const void* __restrict__ dres,
@@ -130,8 +133,8 @@ __global__ __launch_bounds__(ln_bwd_waves<NV>() * 64) void ln_bwd_kernel(const v
             if (c < C) {
                 // the residual gradient is fetched together with x and dy (not after the row reductions): one memory
                 // round trip per row instead of two
-                if (dres) dr[i] = ld4<DR16, NT>(dres, (size_t)row * C + c);
-                const f32x4 xv = ld4<X16, NT>(x, (size_t)row * C + c);
+                if (dres) dr[i] = ld4<DR16, true>(dres, (size_t)row * C + c);
+                const f32x4 xv = ld4<X16, true>(x, (size_t)row * C + c);
                 f32x4 dy;
                 if (DY32) {
                     dy = *(const f32x4*)((const float*)dyv + (size_t)row * C + c);
@@ -161,10 +164,7 @@ __global__ __launch_bounds__(ln_bwd_waves<NV>() * 64) void ln_bwd_kernel(const v
                 for (int e = 0; e < 4; ++e) o[e] = rs * (g[i][e] - c1 - xh[i][e] * c2);
                 o = o + dr[i];
                 if (CS) ac[i] = ac[i] + o;
-                if (dx32) {
-                    if (NT) __builtin_nontemporal_store(o, (f32x4*)(dx32 + (size_t)row * C + c));
-                    else *(f32x4*)(dx32 + (size_t)row * C + c) = o;
-                }
+                if (dx32) __builtin_nontemporal_store(o, (f32x4*)(dx32 + (size_t)row * C + c));
                 if (dx16) {
                     bf16x4 o4 = {f2bf(o[0]), f2bf(o[1]), f2bf(o[2]), f2bf(o[3])};
                     *(bf16x4*)(dx16 + (size_t)row * C + c) = o4;
@@ -438,83 +438,63 @@ int ln_grid(int M) {
     int g = ocn_cdiv(M, 4);
     return g < 2048 ? g : 2048;
 }
-int g_ln_num_cu = 0;
 template <int NV>
 int ln_bwd_grid(int M) {
-    if (g_ln_num_cu == 0) {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        g_ln_num_cu = n;
-    }
     const int g = ocn_cdiv(M, ln_bwd_waves<NV>());
     // developer knob 14: workgroups of the backward's grid
-    const int cap = g_ocn_tuning[14] > 0 ? g_ocn_tuning[14] : g_ln_num_cu;
+    const int cap = g_ocn_tuning[14] > 0 ? g_ocn_tuning[14] : ocn_num_cus();
     return g < cap ? g : cap;
+}
+
+// C -> NV, the 16-byte vectors per lane that hold a row (C <= NV * 256): f(std::integral_constant<int, NV>) and its result
+template <class F>
+auto ln_with_nv(int C, F&& f) {
+    switch (ocn_cdiv(C, 256)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        default: return f(std::integral_constant<int, 8>{});
+    }
 }
 
 template <int NV>
 void launch_fwd(hipStream_t st, const void* x, int x_is_bf16, const float* w, const float* b, bf16* y16, float* y32, float* mean, float* rstd,
                 int M, int C, float eps) {
     const dim3 g(ln_grid(M)), t(256);
-    if (x_is_bf16 && C == NV * 256 && g_ocn_tuning[12] != 2) {  // the pipelined form (developer knob 12 = 2: the one-row-at-a-time kernel on the bf16 stream, A/B)
-        if (y16 && y32) ln_fwd16_kernel<NV, true, true><<<g, t, 0, st>>>((const bf16*)x, w, b, y16, y32, mean, rstd, M, C, eps);
-        else if (y16) ln_fwd16_kernel<NV, true, false><<<g, t, 0, st>>>((const bf16*)x, w, b, y16, y32, mean, rstd, M, C, eps);
-        else ln_fwd16_kernel<NV, false, true><<<g, t, 0, st>>>((const bf16*)x, w, b, y16, y32, mean, rstd, M, C, eps);
-    } else if (x_is_bf16)
-        ln_fwd_kernel<NV, false, true><<<g, t, 0, st>>>(x, w, b, y16, y32, mean, rstd, M, C, eps);
-    else if (g_ocn_tuning[12] == 1)  // developer knob 12 = 1: default cache policy for x
-        ln_fwd_kernel<NV, false, false><<<g, t, 0, st>>>(x, w, b, y16, y32, mean, rstd, M, C, eps);
-    else
-        ln_fwd_kernel<NV, true, false><<<g, t, 0, st>>>(x, w, b, y16, y32, mean, rstd, M, C, eps);
-}
-template <int NV, bool DY32, bool NT, bool CS, bool X16 = false, bool DR16 = false>
-void launch_bwd4(hipStream_t st, const void* dy, const void* x, const float* w, const float* mean, const float* rstd, const void* dres, float* dx32,
-                 bf16* dx16, float* dw, float* db, float* dcol, float* det_ws, int M, int C) {
-    const int G = ln_bwd_grid<NV>(M);
-    ln_bwd_kernel<NV, DY32, NT, CS, X16, DR16><<<dim3(G), dim3(ln_bwd_waves<NV>() * 64), 0, st>>>(dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);
-    if (det_ws) ln_bwd_finish_kernel<<<dim3(ocn_cdiv(C, 256)), dim3(256), 0, st>>>(det_ws, G, C, dw, db, dcol);
+    if (x_is_bf16 && C == NV * 256) {  // the pipelined form
+        const auto k = (y16 && y32) ? ln_fwd16_kernel<NV, true, true> : (y16 ? ln_fwd16_kernel<NV, true, false> : ln_fwd16_kernel<NV, false, true>);
+        k<<<g, t, 0, st>>>((const bf16*)x, w, b, y16, y32, mean, rstd, M, C, eps);
+    } else {
+        const auto k = x_is_bf16 ? ln_fwd_kernel<NV, true> : ln_fwd_kernel<NV, false>;
+        k<<<g, t, 0, st>>>(x, w, b, y16, y32, mean, rstd, M, C, eps);
+    }
 }
 // returns false for a dtype combination that has no instantiation (the caller reports it)
 template <int NV>
 bool launch_bwd(hipStream_t st, const void* dy, int dy_is_f32, const void* x, int x_is_bf16, const float* w, const float* mean,
                 const float* rstd, const void* dres, int dres_is_bf16, float* dx32, bf16* dx16, float* dw, float* db, float* dcol, float* det_ws, int M, int C) {
-    if (x_is_bf16) {
-        // the bf16 residual stream (image tower): dy is always the bf16 output of a dgrad GEMM there; the residual gradient is bf16 (the
-        // reference's autograd: the gradient of a bf16 tensor is bf16) or the fp32 companion (NativeCLIP(image_stream="bf16-fp32grad"))
-        if (dy_is_f32 || dcol) return false;
-        // the pipelined form up to C = 1280 (ViT-H-14; 8 waves of up to 256 registers there; beyond, the second row's registers spill; developer knob
-        // 8 = 2: the one-row-at-a-time kernel, A/B)
-        if constexpr (NV <= 5) if (dx16 && C == NV * 256 && g_ocn_tuning[8] != 2) {
-            const int G = ln_bwd_grid<NV>(M);  // (the reproducible form's workspace is sized for this grid; rows are grid-strided)
-            const dim3 g(G), t(ln_bwd16_waves<NV>() * 64);
-#define OCN_LN_BWD16(DR)                                                                                                                                   \
-    {                                                                                                                                                     \
-        if (dx32) ln_bwd16_kernel<NV, DR, true><<<g, t, 0, st>>>((const bf16*)dy, (const bf16*)x, w, mean, rstd, dres, dx32, dx16, dw, db, det_ws, M, C);  \
-        else ln_bwd16_kernel<NV, DR, false><<<g, t, 0, st>>>((const bf16*)dy, (const bf16*)x, w, mean, rstd, dres, dx32, dx16, dw, db, det_ws, M, C);      \
+    // the bf16 residual stream (image tower): dy is always the bf16 output of a dgrad GEMM there; the residual gradient is bf16 (the
+    // reference's autograd: the gradient of a bf16 tensor is bf16) or the fp32 companion (NativeCLIP(image_stream="bf16-fp32grad"))
+    if (x_is_bf16 ? (dy_is_f32 || dcol) : (dres && dres_is_bf16)) return false;
+    const int G = ln_bwd_grid<NV>(M);  // (the reproducible form's workspace is sized for this grid; rows are grid-strided)
+    bool pipelined = false;
+    // the pipelined form up to C = 1280 (ViT-H-14; 8 waves of up to 256 registers there; beyond, the second row's registers spill)
+    if constexpr (NV <= 5) if (x_is_bf16 && dx16 && C == NV * 256) {
+        const auto k = !dres ? (dx32 ? ln_bwd16_kernel<NV, 0, true> : ln_bwd16_kernel<NV, 0, false>)
+                     : dres_is_bf16 ? (dx32 ? ln_bwd16_kernel<NV, 1, true> : ln_bwd16_kernel<NV, 1, false>)
+                                    : (dx32 ? ln_bwd16_kernel<NV, 2, true> : ln_bwd16_kernel<NV, 2, false>);
+        k<<<dim3(G), dim3(ln_bwd16_waves<NV>() * 64), 0, st>>>((const bf16*)dy, (const bf16*)x, w, mean, rstd, dres, dx32, dx16, dw, db, det_ws, M, C);
+        pipelined = true;
     }
-            if (!dres) OCN_LN_BWD16(0) else if (dres_is_bf16) OCN_LN_BWD16(1) else OCN_LN_BWD16(2)
-#undef OCN_LN_BWD16
-            if (det_ws) ln_bwd_finish_kernel<<<dim3(ocn_cdiv(C, 256)), dim3(256), 0, st>>>(det_ws, G, C, dw, db, dcol);
-            return true;
-        }
-        if (dres && dres_is_bf16) launch_bwd4<NV, false, true, false, true, true>(st, dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);
-        else launch_bwd4<NV, false, true, false, true, false>(st, dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);
-        return true;
+    if (!pipelined) {  // <NV, DY32, CS, X16, DR16>
+        const auto k = x_is_bf16 ? ((dres && dres_is_bf16) ? ln_bwd_kernel<NV, false, false, true, true> : ln_bwd_kernel<NV, false, false, true, false>)
+                     : dy_is_f32 ? (dcol ? ln_bwd_kernel<NV, true, true> : ln_bwd_kernel<NV, true, false>)
+                                 : (dcol ? ln_bwd_kernel<NV, false, true> : ln_bwd_kernel<NV, false, false>);
+        k<<<dim3(G), dim3(ln_bwd_waves<NV>() * 64), 0, st>>>(dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);
     }
-    if (dres && dres_is_bf16) return false;
-    const bool nt = g_ocn_tuning[8] != 1;  // developer knob 8 = 1: default cache policy everywhere
-#define OCN_LN_BWD(DY32, NT)                                                                                                  \
-    {                                                                                                                         \
-        if (dcol) launch_bwd4<NV, DY32, NT, true>(st, dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);     \
-        else launch_bwd4<NV, DY32, NT, false>(st, dy, x, w, mean, rstd, dres, dx32, dx16, dw, db, dcol, det_ws, M, C);         \
-    }
-    if (dy_is_f32) {
-        if (nt) OCN_LN_BWD(true, true) else OCN_LN_BWD(true, false)
-    } else {
-        if (nt) OCN_LN_BWD(false, true) else OCN_LN_BWD(false, false)
-    }
-#undef OCN_LN_BWD
+    if (det_ws) ln_bwd_finish_kernel<<<dim3(ocn_cdiv(C, 256)), dim3(256), 0, st>>>(det_ws, G, C, dw, db, dcol);
     return true;
 }
 
@@ -538,29 +518,14 @@ extern "C" int ocn_layernorm_fwd(const void* x, int x_is_bf16, const float* w, c
     OCN_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && C <= 2048, "ocn_layernorm_fwd: bad shape M=%d C=%d", M, C);
     hipStream_t st = (hipStream_t)stream;
     bf16* y16 = (bf16*)y_bf16;
-    switch (ocn_cdiv(C, 256)) {
-        case 1: launch_fwd<1>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-        case 2: launch_fwd<2>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-        case 3: launch_fwd<3>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-        case 4: launch_fwd<4>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-        case 5: launch_fwd<5>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-        default: launch_fwd<8>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); break;
-    }
+    ln_with_nv(C, [&](auto nv) { launch_fwd<decltype(nv)::value>(st, x, x_is_bf16, w, b, y16, y_f32, mean, rstd, M, C, eps); });
     OCN_CHECK_LAUNCH("ocn_layernorm_fwd");
     return OCN_OK;
 }
 
 // floats of workspace the reproducible form of ocn_layernorm_bwd needs: one [3][C] slab per workgroup of its grid
 extern "C" int64_t ocn_layernorm_bwd_det_workspace_floats(int M, int C) {
-    int g = 0;
-    switch (ocn_cdiv(C, 256)) {
-        case 1: g = ln_bwd_grid<1>(M); break;
-        case 2: g = ln_bwd_grid<2>(M); break;
-        case 3: g = ln_bwd_grid<3>(M); break;
-        case 4: g = ln_bwd_grid<4>(M); break;
-        case 5: g = ln_bwd_grid<5>(M); break;
-        default: g = ln_bwd_grid<8>(M); break;
-    }
+    const int g = ln_with_nv(C, [&](auto nv) { return ln_bwd_grid<decltype(nv)::value>(M); });
     return (int64_t)g * 3 * C;
 }
 
@@ -580,15 +545,9 @@ extern "C" int ocn_layernorm_bwd(const void* dy, int dy_is_f32, const void* x, i
     OCN_CHECK_ARG(M > 0 && C > 0 && C % 4 == 0 && C <= 2048, "ocn_layernorm_bwd: bad shape M=%d C=%d", M, C);
     hipStream_t st = (hipStream_t)stream;
     bf16* dx16 = (bf16*)dx_bf16;
-    bool ok = true;
-    switch (ocn_cdiv(C, 256)) {
-        case 1: ok = launch_bwd<1>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-        case 2: ok = launch_bwd<2>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-        case 3: ok = launch_bwd<3>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-        case 4: ok = launch_bwd<4>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-        case 5: ok = launch_bwd<5>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-        default: ok = launch_bwd<8>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C); break;
-    }
+    const bool ok = ln_with_nv(C, [&](auto nv) {
+        return launch_bwd<decltype(nv)::value>(st, dy, dy_is_f32, x, x_is_bf16, w, mean, rstd, dres, dres_is_bf16, dx_f32, dx16, dw, db, dcol, det_workspace, M, C);
+    });
     OCN_CHECK_ARG(ok, "ocn_layernorm_bwd: unsupported dtype combination (bf16 x needs bf16 dy and no dcol; a bf16 residual gradient needs bf16 x)");
     OCN_CHECK_LAUNCH("ocn_layernorm_bwd");
     return OCN_OK;

@@ -37,6 +37,9 @@ void ocn_set_error(const char* fmt, ...);
         }                                                                           \
     } while (0)
 
+// compute units of the device that was current at the first call (256 if the query fails); cached per process (core.hip)
+int ocn_num_cus();
+
 // ---- small device helpers ----------------------------------------------------------------------
 OCN_DEV float bf2f(bf16 v) { return (float)v; }
 OCN_DEV bf16 f2bf(float v) { return (bf16)v; }  // round-to-nearest-even (v_cvt_pk_bf16_f32 on gfx950)

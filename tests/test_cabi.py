@@ -84,6 +84,21 @@ def test_attention_and_token_embed_layout_rules(lib_path):
         _lib.call("ocn_token_embed_bwd", p, p, p, 0, p, p, None, B, 77, 100, 64, 1000, 0, 0)
 
 
+def test_removed_wgrad_variants_are_refused(lib_path):
+    """ocn_set_gemm_variant's TN values 6 / 7 chose between two main loops of the hand-scheduled wgrad kernel; one loop is left, and a tool that
+    still asks for either must fail (host-side check, no launch) instead of timing one kernel twice.  The values that remain are accepted."""
+    from open_clip_amd import _lib
+    try:
+        for tn in (6, 7):
+            with pytest.raises(RuntimeError, match=rf"ocn_set_gemm_variant failed \(-1\): ocn_set_gemm_variant: TN value {tn} is gone"):
+                _lib.call("ocn_set_gemm_variant", (tn << 4) | 5)
+        for tn in (0, 1, 3):
+            for nt in (0, 4, 5, 6, 7):
+                _lib.call("ocn_set_gemm_variant", (tn << 4) | nt)
+    finally:
+        _lib.call("ocn_set_gemm_variant", 0)
+
+
 def test_library_contains_gfx950_code_object(lib_path):
     data = open(lib_path, "rb").read()
     assert b"gfx950" in data

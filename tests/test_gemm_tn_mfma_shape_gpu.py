@@ -1,5 +1,5 @@
-"""The hand-scheduled wgrad kernel under both MFMA shapes of its main loop (``ocn_set_gemm_variant`` TN field 6 = 32x32x16, 7 = 16x16x32) on integer
-operands (tests/gemm_exact.py): every reduction order is exact, so dW and dbias are bit-equal to the integer result, the two variants and the
+"""The hand-scheduled wgrad kernel and its 16x16x32 MFMA main loop (forced with ``ocn_set_gemm_variant`` TN field 3) on integer
+operands (tests/gemm_exact.py): every reduction order is exact, so dW and dbias are bit-equal to the integer result, the atomic and the
 deterministic form bit-equal to each other, and the sentinels around dW and dbias untouched.  The operands are random and asymmetric: a store map
 with rows and columns swapped, a fragment read that takes another lane group's reduction rows, a bias strip summed twice or not at all each change
 a bit.  Cases: the smallest 'big' shape and a shape with ragged N and K tiles on three layouts; a zero-filled tail of every length that ends on
@@ -15,8 +15,8 @@ from tests import gemm_exact as X  # noqa: E402
 DEV = "cuda:0"
 NAN = float("nan")
 P = X.PAD_ROWS
-SHAPE_32, SHAPE_16 = 6, 7  # TN field of ocn_set_gemm_variant
-MODES = (SHAPE_32, SHAPE_16, "det")
+HAND = 3  # TN field of ocn_set_gemm_variant: the hand-scheduled kernel whatever the size of the product
+MODES = (HAND, "det")
 
 
 @pytest.fixture(autouse=True)
@@ -83,16 +83,14 @@ def _case(shape, layout, settings=((True, 1.0), (False, 0.25))):
         for mode in MODES:
             tag = f"wgrad MFMA shape [{_sid(shape)}] {layout} mode {mode} alpha={alpha}{' +dbias' if bias else ''}{' rescue' if ops.tile_rescue() else ''}"
             got[mode] = _run(o, shape, layout, mode, bias, alpha, tag)
-        for mode in (SHAPE_32, SHAPE_16):
-            assert torch.equal(got[mode][0], got["det"][0]) and torch.equal(got[mode][1], got["det"][1]), \
-                f"[{_sid(shape)}] {layout}: variant {mode} != deterministic form"
-        assert torch.equal(got[SHAPE_32][0], got[SHAPE_16][0]) and torch.equal(got[SHAPE_32][1], got[SHAPE_16][1])
+        assert torch.equal(got[HAND][0], got["det"][0]) and torch.equal(got[HAND][1], got["det"][1]), \
+            f"[{_sid(shape)}] {layout}: variant {HAND} != deterministic form"
 
 
 @pytest.mark.parametrize("layout", ["contig", "A_cols", "dW_rows"])
 @pytest.mark.parametrize("shape", [(8203, 512, 512), (3000, 640, 328)], ids=_sid)
 def test_smallest_and_ragged_shapes(shape, layout):
-    """(8203, 512, 512): the smallest shape that is 'big', ragged M; (3000, 640, 328): ragged N and K tiles, reached through the forced variants"""
+    """(8203, 512, 512): the smallest shape that is 'big', ragged M; (3000, 640, 328): ragged N and K tiles, reached through the forced variant"""
     _case(shape, layout)
 
 
@@ -105,7 +103,7 @@ def test_zero_filled_tail_against_the_lane_group_map(r):
 
 @pytest.mark.parametrize("shape", [(8203, 512, 512), (3000, 264, 520)], ids=_sid)
 def test_bias_slices(shape):
-    """tiles_k = 2, and 3 with a ragged last k-tile (N = 264: a ragged n-tile too; forced through the variants): every step's column sums are
+    """tiles_k = 2, and 3 with a ragged last k-tile (N = 264: a ragged n-tile too; forced through the variant): every step's column sums are
     taken by exactly one of the workgroups that share the strip, each of its 16-wide blocks by exactly one wave"""
     assert (shape[2] + 255) // 256 == (2 if shape[2] == 512 else 3)
     _case(shape, "contig", settings=((True, 1.0),))
@@ -113,7 +111,7 @@ def test_bias_slices(shape):
 
 @pytest.mark.parametrize("bias", [True, False], ids=["dbias", "nodbias"])
 def test_paired_launch(bias):
-    """ocn_gemm_tn_accum2 under variant 7: both problems bit-equal to the integer result and to two single launches"""
+    """ocn_gemm_tn_accum2 under variant 3: both problems bit-equal to the integer result and to two single launches"""
     M, C = 8203, 256
     assert M * 4 * C * C >= 2 ** 31 and C >= 256  # what sends the pair to the one-launch kernel
     g = torch.Generator(device=DEV).manual_seed(M + C)
@@ -129,7 +127,7 @@ def test_paired_launch(bias):
     q2, e2 = X.embed(d2[:, None], P, 0, 1, X.SENTINEL)
     s1, s2, f1, f2 = w1.clone(), w2.clone(), d1.clone(), d2.clone()
     try:
-        _lib.call("ocn_set_gemm_variant", SHAPE_16 << 4)
+        _lib.call("ocn_set_gemm_variant", HAND << 4)
         ops.gemm_tn_accum2(a1, b1, o1, e1[:, 0] if bias else None, a2, b2, o2, e2[:, 0] if bias else None)
         ops.gemm_tn_accum(a1, b1, s1, f1 if bias else None)
         ops.gemm_tn_accum(a2, b2, s2, f2 if bias else None)
@@ -146,7 +144,7 @@ def test_paired_launch(bias):
 
 
 def test_rescue_form_nothing_held():
-    """ops.set_tile_rescue(True) with no workgroup held back: the rescue instantiations of both shapes (the fixture restores the defaults)"""
+    """ops.set_tile_rescue(True) with no workgroup held back: the rescue instantiations (the fixture restores the defaults)"""
     ops.set_tile_rescue(True)
     assert ops.tile_rescue()
     _case((8203, 512, 512), "contig")

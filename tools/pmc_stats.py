@@ -63,7 +63,7 @@ def main():
                 key = k.split("(")[0].replace(", ", ",")
                 # the static instantiations (last template argument RESCUE = false, round 6) keep the names bench.py has used since round 1
                 key = re.sub(r"^(gemm_nt5_kernel<\d+,false,\d+),false>$", r"\1>", key)
-                # (gemm_tn5_kernel<BIAS, RESCUE, MF16>: both MFMA shapes of its main loop are the same kernel to bench.py)
+                # (gemm_tn5_kernel<BIAS, RESCUE>; traces taken while it had two main loops carry a third argument, MF16)
                 key = re.sub(r"^(gemm_tn5_kernel<(?:true|false)),false(?:,(?:true|false))?>$", r"\1>", key)
                 rec["by_kernel"][key] = {"launches": n, "read_bytes_per_launch": rd * 1e6, "write_bytes_per_launch": (wr if wr == wr else 0.0) * 1e6,
                                          "bytes_per_launch": (rd + (wr if wr == wr else 0.0)) * 1e6}

@@ -158,24 +158,6 @@ def ntstore_sweep():
     _lib.call("ocn_set_gemm_variant", 0)
 
 
-def ln_sweep():
-    """LayerNorm backward with / without the non-temporal policy on its read-once operands (developer knob 8)"""
-    for M, C in [(Mi, 768), (Mt, 512)]:
-        x, dres = torch.randn(M, C, device=dev), torch.randn(M, C, device=dev)
-        dy = torch.randn(M, C, device=dev).bfloat16()
-        w = torch.ones(C, device=dev)
-        mean, rstd = torch.zeros(M, device=dev), torch.ones(M, device=dev)
-        dw, db = torch.zeros(C, device=dev), torch.zeros(C, device=dev)
-        row = []
-        gb = M * C * 16 / 1e9
-        for knob in (0, 1, 0, 1):
-            _lib.call("ocn_set_tuning", 8, knob)
-            ms = timeit(lambda: ops.layernorm_bwd(dy, x, w, mean, rstd, dw, db, dres=dres, want_f32=True, want_bf16=True))
-            row.append(f"{'default' if knob else 'non-temporal'} {ms:.3f} ms ({gb / ms:.2f} TB/s)")
-        _lib.call("ocn_set_tuning", 8, 0)
-        print(f"ln_bwd [{M}x{C}]: " + " | ".join(row), flush=True)
-
-
 def percu_sweep():
     """persistent NT GEMM launched with k workgroups per CU (developer knob 10), steady-state timing on the step's shapes"""
     cases = [("img qkv", Mi, 2304, 768, 0), ("img dh2", Mi, 768, 3072, 0), ("img da", Mi, 768, 768, 0), ("img dh1", Mi, 768, 2304, 0),
@@ -262,8 +244,6 @@ if __name__ == "__main__":
         nt_sweep()
     if what in ("all", "percu"):
         percu_sweep()
-    if what in ("all", "ln"):
-        ln_sweep()
     if what in ("all", "ntstore"):
         ntstore_sweep()
     if what in ("all", "stagger"):
